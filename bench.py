@@ -14,6 +14,7 @@ and the counter arrays are summed with one RCCL all-reduce per step.
 
     python bench.py                                   # N=1, 10 M reads
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+    python bench.py --dump-outputs DIR                # also writes the last timed step's hits and counters as .npy
 
 Before the W warmup steps the setup runs `--preheat` (30) untimed scans of the same batch: in a
 fresh process the GPU clocks take about ten steps (20 ms) to settle, and without it the first timed
@@ -63,7 +64,7 @@ def analytic_chunk_offsets(n_records, rb, L):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps (ms_per_step = their wall time / steps)')
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--reads', type=int, default=10_000_000, help='records per GPU')
     ap.add_argument('--readlen', type=int, default=150)
@@ -85,7 +86,12 @@ def main():
     ap.add_argument('--total-reads', type=int, default=0,
                     help='records of the WHOLE job, split evenly over the ranks (strong scaling): `--gpus 8 --total-reads 40000000` is '
                          'BASELINE.json configs[3]; without it every rank scans --reads records (weak scaling)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one handed its caller (ordered hits, hit bytes, counter array) '
+                         'as DIR/<name>.npy, float64 / float32, at most 64 MB in all (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` by itself: this process becomes the launcher of N ranks (the join of the reference's
@@ -311,6 +317,12 @@ def main():
         total_hits = r['n_hits']
         assert total_records == n, 'records lost: %d of %d' % (total_records, n)
 
+    # (before the steps below reset the scanners: the last timed step's arrays are still the library's)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, scanners[(args.steps - 1) % depth],
+                              ctr.cpu().numpy() if ctr is not None else r['counters'])
+
     # SURVEY 8(d) defines t_kernel as the sum of ALL device kernels of a scan: HIP events of the library around everything a
     # step enqueues (table upload, tile tables, scan, validation, redo chain, fold, ordering, copies) only mean that when
     # one step runs at a time, so five more steps are run strictly one after the other behind the timed region
@@ -353,7 +365,7 @@ def main():
                                   'seed-filter k=%d (%d of %d sequences)' % (table.seed_k, sum(table.seeded), table.nseq),
                    'join_checked': join_checked,
                    'hits_per_step': total_hits, 'records_per_step': total_records,
-                   'preheat_steps': max(0, args.preheat), 'steps_in_flight': depth},
+                   'preheat_steps': max(0, args.preheat), 'steps_in_flight': depth, 'outputs_dumped': dumped},
         'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                      'frac': achieved / HBM_PEAK_GBS, 'traffic': None,
                      'kernel': 'kvq_scan_bp' if any(table.seeded) and not args.exhaustive else 'kvq_match_all',
@@ -463,6 +475,51 @@ def source_sha256():
         with open(path, 'rb') as f:
             h.update(f.read())
     return h.hexdigest()
+
+
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs writes at most this much array data (64 MB with the .npy headers)
+
+
+def dump_outputs(path, sc, counters):
+    """--dump-outputs: what one step hands its caller, from scanner `sc` after its finish, as path/<name>.npy --
+    the ordered hits (hit_seq_nr, hit_file_pos, hit_seq_pos, hit_length, hit_readlength), the length and bytes of
+    each hit (hitseq_length, hitseq_bytes: the hits' bytes one after the other) and the counter array (counters).
+    Integers go out as float64 (exact below 2**53), the hit bytes as float32.  Beyond DUMP_BYTES a fixed, seeded
+    sample is written instead, in stored order, and <name>_index.npy holds the positions taken.  -> summary dict"""
+    os.makedirs(path, exist_ok=True)
+    h = sc.hit_arrays()
+    counters = np.asarray(counters)
+    out = {}
+    ctr_budget = DUMP_BYTES // 2
+    if counters.size * 8 > ctr_budget:
+        idx = np.sort(np.random.default_rng(1).choice(counters.size, ctr_budget // 16, replace=False))
+        out['counters_index'], counters = idx, counters[idx]
+    out['counters'] = counters
+    off = h['offsets']
+    lens = np.diff(off)
+    n = len(lens)
+    per_hit = 8 * 7 + 4 * (int(lens.max()) if n else 0)            # six arrays, the index, the longest hit's bytes
+    keep = (DUMP_BYTES - counters.size * 16) // per_hit
+    if n > keep:
+        idx = np.sort(np.random.default_rng(2).choice(n, keep, replace=False))
+        out['hit_index'] = idx
+    else:
+        idx = np.arange(n)
+    for k in ('seq_nr', 'file_pos', 'seq_pos', 'length', 'readlength'):
+        out['hit_' + k] = h[k][idx]
+    out['hitseq_length'] = lens[idx]
+    pieces = [h['blob'][off[i]:off[i + 1]] for i in idx] if len(idx) < n else [h['blob']]
+    hit_bytes = np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.uint8)
+    total = 0
+    for name, a in out.items():
+        a = np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(path, name + '.npy'), a)
+        total += a.nbytes
+    a = hit_bytes.astype(np.float32)
+    np.save(os.path.join(path, 'hitseq_bytes.npy'), a)
+    total += a.nbytes
+    assert total <= DUMP_BYTES, total
+    return {'dir': path, 'hits': n, 'hits_written': len(idx), 'counters': int(sc.table.counters_len), 'bytes': total}
 
 
 def end_to_end(d_data, n, rb, seqs, cfg, nthreads=8):
