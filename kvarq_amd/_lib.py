@@ -10,6 +10,7 @@ PATH = os.path.join(HERE, 'libkvarq_hip.so')
 MAX_READLENGTH = 1024
 OK, ERR_FORMAT, ERR_IO, ERR_MEMORY, ERR_RUNTIME, ERR_TYPE, ERR_DEVICE, ERR_RESCAN = range(8)
 CTR_RECORDS, CTR_LONGEST, CTR_HITS, CTR_READLENGTHS = 0, 1, 2, 4
+CELL_DENSE, CELL_DIAG, CELL_STAMPS = 0x1000, 0x2000, 0x4000      # kvq_scan_kernel_pick / kvq_scan_kernel
 
 
 class Config(C.Structure):
@@ -73,6 +74,9 @@ PROTOTYPES = {
     'kvq_scan_reset': (i32, [vp]),
     'kvq_scan_path': (i32, [vp]),
     'kvq_scan_force_exhaustive': (None, [vp, i32]),
+    'kvq_scan_kernel_pick': (i32, [i32, i32, i32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    'kvq_scan_kernel': (i32, [vp]),
+    'kvq_tile_for_text': (C.c_uint32, [vp, C.c_size_t, P(C.c_uint32)]),
     'kvq_comm_unique_id': (i32, [vp]),
     'kvq_comm_create': (vp, [i32, i32, vp]),
     'kvq_comm_destroy': (None, [vp]),
@@ -129,6 +133,13 @@ def lib():
             f.restype, f.argtypes = res, args
         _lib = L
     return _lib
+
+
+def kernel_cell(cell):
+    """a kvq_scan_kernel_pick / kvq_scan_kernel word as {'k', 'stride', 'lg', 'dense'} (None for 0 = no seed-filter launch)"""
+    if cell <= 0:
+        return None
+    return {'k': cell & 15, 'stride': (cell >> 4) & 15, 'lg': ((cell >> 8) & 15) - 1, 'dense': bool(cell & CELL_DENSE)}
 
 
 def last_error():

@@ -423,7 +423,7 @@ void kvq_probe_text(const uint8_t *text, size_t n, uint32_t &maxline, uint32_t &
     maxline = std::max<uint32_t>(best, (uint32_t)(n - start));
     rec_bytes = lines >= 16 ? (uint32_t)(start * 4 / lines) : 0u;           // (start = bytes in whole lines)
 }
-uint32_t kvq_tile_for_text(const uint8_t *text, size_t n, uint32_t *rec_bytes_out)
+extern "C" uint32_t kvq_tile_for_text(const uint8_t *text, size_t n, uint32_t *rec_bytes_out)
 {
     uint32_t maxline, rec_bytes;
     kvq_probe_text(text, n, maxline, rec_bytes);

@@ -128,6 +128,7 @@ struct kvq_scan {
     unsigned int *d_arena_n = nullptr, *d_range = nullptr, *d_fail = nullptr, *cur_fail = nullptr;
     unsigned long long *d_blob_n = nullptr, *d_err = nullptr, *d_err_stage = nullptr, *d_stage_ctr = nullptr;
     int path_bits = 0;
+    int32_t kernel_cell = 0;           // the kvq_scan_bp instantiation of the last seed-filter launch (kvq_scan_kernel_pick)
     std::vector<int64_t> cur_chunk_off;  // chunk offsets of the batch being enqueued
     size_t cur_co_at = 0;                // ... and where run_batch put them in the pool
     size_t cur_skip_at = 0, cur_first_at = 0; uint32_t cur_ntiles = 0;   // the batch's list of skipped tiles, its first-tile table
@@ -177,7 +178,7 @@ int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, in
 
 uint32_t kvq_choose_tile(uint32_t maxline, uint32_t rec_bytes);
 uint32_t kvq_min_tile();
-uint32_t kvq_tile_for_text(const uint8_t *text, size_t n, uint32_t *rec_bytes_out = nullptr);
+int32_t  kvq_scan_pick(int k, int stride, bool ix_dense, uint32_t rec_bytes, uint32_t tile_bytes, uint32_t dbg, int lg_env, int dense_env);   // (kvq_launch.hip)
 
 // synth.hip
 // (C ABI only)

@@ -6,6 +6,43 @@
 // launch (both scan kernels)
 // ---------------------------------------------------------------------------
 
+// Which instantiation of kvq_scan_bp scans a batch: the seed length, the stride of the index, the lane group and
+// the kernel family (the draining kernels for seeds shorter than 8 and for tables dense in the code space).  A
+// pure function of its arguments, so that the tests can pin every choice without a GPU; kvq_seeded_launch takes
+// the kernel it names.  lg_env / dense_env: the KVQ_LG / KVQ_DENSE switches (-2 / -1: not set).
+int32_t kvq_scan_pick(int k, int stride, bool ix_dense, uint32_t rec_bytes, uint32_t tile_bytes, uint32_t dbg, int lg_env, int dense_env)
+{
+    if (k < 5 || k > 8 || (stride != 2 && stride != 4 && stride != 8)) return -1;
+    const bool st = (dbg & 16u) != 0;
+    // the lane group of a read: four lanes, fixed at compile time, when that is the widest power of two
+    // that gives every read of a full tile its own lanes (records of 100 to 250 bases); otherwise the
+    // kernel that works the width out per tile
+    // (with a KVQ_DBG switch set: the instantiations that honour them -- the general kernel and the four-lane one)
+    int lg = -1;
+    if (rec_bytes >= 40u) {
+        const uint32_t n_full = tile_bytes / rec_bytes + 1u;                 // records a full tile can own
+        if (n_full <= 128u && n_full > 64u) lg = 2;
+        else if (n_full <= 64u && n_full > 32u) lg = 3;                      // (eight lanes a read: records of 250 to 550 bases)
+        else if (n_full <= 256u && n_full > 128u) lg = 1;                    // (two lanes a read: records of 50 to 125 bases)
+    }
+    if (lg_env >= -1) lg = lg_env >= 1 && lg_env <= 3 ? lg_env : -1;
+    if ((lg == 3 || lg == 1) && st) lg = -1;                                // (no instrumented build of those)
+    // (seeds shorter than 8 -- (maxerrors + 1) * 8 above the shortest accepted overlap: kvq_seed_k -- have the general and the four-lane
+    // kernel, both draining; so have 8-base seeds on a table that is dense in the code space)
+    const bool dense = k == 8 && !st && (dense_env >= 0 ? dense_env != 0 : ix_dense);
+    const bool diag = ((dbg & ~16u) && !st) || k != 8 || dense;
+    if (diag && lg != 2) lg = -1;
+    return (int32_t)k | (int32_t)stride << 4 | (int32_t)(lg + 1) << 8 | (k < 8 || dense ? KVQ_CELL_DENSE : 0) |
+           (diag ? KVQ_CELL_DIAG : 0) | (st && !diag ? KVQ_CELL_STAMPS : 0);
+}
+
+extern "C" int32_t kvq_scan_kernel_pick(int32_t k, int32_t stride, int32_t dense, uint32_t rec_bytes, uint32_t tile_bytes, uint32_t dbg)
+{
+    return kvq_scan_pick(k, stride, dense != 0, rec_bytes, tile_bytes, dbg, -2, -1);
+}
+
+extern "C" int32_t kvq_scan_kernel(const kvq_scan *s) { return s->kernel_cell; }
+
 int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, int64_t nbytes,
                       const uint32_t *d_chunk_off, int64_t nchunks, int64_t fpos_base, uint32_t max_chunk_bytes)
 {
@@ -104,12 +141,7 @@ int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, in
     const bool timed = !s->ev_main.empty();
     if (timed) KVQ_HIP(hipEventRecord(s->ev_main.back().first, s->stream));
     typedef void (*BpKernel)(const BpArgs *);
-    const int si = ix->stride == 8 ? 2 : ix->stride == 4 ? 1 : 0, st = (dbg & 16u) ? 3 : 0;
     {
-        // the lane group of a read: four lanes, fixed at compile time, when that is the widest power of two
-        // that gives every read of a full tile its own lanes (records of 100 to 250 bases); otherwise the
-        // kernel that works the width out per tile
-        // (with a KVQ_DBG switch set: the instantiations that honour them -- the general kernel and the four-lane one)
         static const BpKernel kernels_diag[6] = { kvq_scan_bp<2, -1, false, true>, kvq_scan_bp<4, -1, false, true>, kvq_scan_bp<8, -1, false, true>,
                                                   kvq_scan_bp<2, 2, false, true>, kvq_scan_bp<4, 2, false, true>, kvq_scan_bp<8, 2, false, true> };
         static const BpKernel kernels_bp[18] = { kvq_scan_bp<2, -1, false>, kvq_scan_bp<4, -1, false>, kvq_scan_bp<8, -1, false>,
@@ -118,32 +150,24 @@ int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, in
                                                  kvq_scan_bp<2, 2, true>, kvq_scan_bp<4, 2, true>, kvq_scan_bp<8, 2, true>,
                                                  kvq_scan_bp<2, 3, false>, kvq_scan_bp<4, 3, false>, kvq_scan_bp<8, 3, false>,
                                                  kvq_scan_bp<2, 1, false>, kvq_scan_bp<4, 1, false>, kvq_scan_bp<8, 1, false> };
-        static const int lg_env = getenv("KVQ_LG") ? atoi(getenv("KVQ_LG")) : -2;
-        int lg = -1;
-        if (s->rec_bytes >= 40u) {
-            const uint32_t n_full = TILE / s->rec_bytes + 1u;                    // records a full tile can own
-            if (n_full <= 128u && n_full > 64u) lg = 2;
-            else if (n_full <= 64u && n_full > 32u) lg = 3;                      // (eight lanes a read: records of 250 to 550 bases)
-            else if (n_full <= 256u && n_full > 128u) lg = 1;                    // (two lanes a read: records of 50 to 125 bases)
-        }
-        if (lg_env >= -1) lg = lg_env >= 1 && lg_env <= 3 ? lg_env : -1;
-        if ((lg == 3 || lg == 1) && st) lg = -1;                                // (no instrumented build of those)
-        // (seeds shorter than 8 -- (maxerrors + 1) * 8 above the shortest accepted overlap: kvq_seed_k -- have the general and the four-lane kernel)
         static const BpKernel kernels_k5[6] = { kvq_scan_bp<2, -1, false, true, 5>, kvq_scan_bp<4, -1, false, true, 5>, kvq_scan_bp<8, -1, false, true, 5>,
                                                 kvq_scan_bp<2, 2, false, true, 5>, kvq_scan_bp<4, 2, false, true, 5>, kvq_scan_bp<8, 2, false, true, 5> };
         static const BpKernel kernels_k6[6] = { kvq_scan_bp<2, -1, false, true, 6>, kvq_scan_bp<4, -1, false, true, 6>, kvq_scan_bp<8, -1, false, true, 6>,
                                                 kvq_scan_bp<2, 2, false, true, 6>, kvq_scan_bp<4, 2, false, true, 6>, kvq_scan_bp<8, 2, false, true, 6> };
         static const BpKernel kernels_k7[6] = { kvq_scan_bp<2, -1, false, true, 7>, kvq_scan_bp<4, -1, false, true, 7>, kvq_scan_bp<8, -1, false, true, 7>,
                                                 kvq_scan_bp<2, 2, false, true, 7>, kvq_scan_bp<4, 2, false, true, 7>, kvq_scan_bp<8, 2, false, true, 7> };
-        // (8-base seeds on a table that is dense in the code space: the draining kernels)
         static const BpKernel kernels_dense[6] = { kvq_scan_bp<2, -1, false, true, 8, true>, kvq_scan_bp<4, -1, false, true, 8, true>, kvq_scan_bp<8, -1, false, true, 8, true>,
                                                    kvq_scan_bp<2, 2, false, true, 8, true>, kvq_scan_bp<4, 2, false, true, 8, true>, kvq_scan_bp<8, 2, false, true, 8, true> };
+        static const int lg_env = getenv("KVQ_LG") ? atoi(getenv("KVQ_LG")) : -2;
         static const int dense_env = getenv("KVQ_DENSE") ? atoi(getenv("KVQ_DENSE")) : -1;      // (tests: 1 forces the draining kernels, 0 the halving ones)
-        const bool dense = ix->k == 8 && !st && (dense_env >= 0 ? dense_env != 0 : ix->dense);
-        const bool diag = ((dbg & ~16u) && !st) || ix->k != 8 || dense;
-        if (diag && lg != 2) lg = -1;
-        const BpKernel *const dk = ix->k == 5 ? kernels_k5 : ix->k == 6 ? kernels_k6 : ix->k == 7 ? kernels_k7 : dense ? kernels_dense : kernels_diag;
-        const BpKernel kern = diag ? dk[(lg == 2 ? 3 : 0) + si] : kernels_bp[lg == 3 ? 12 + si : lg == 1 ? 15 + si : (lg == 2 ? 6 : 0) + si + st];
+        const int32_t cell = kvq_scan_pick(ix->k, ix->stride, ix->dense, s->rec_bytes, TILE, dbg, lg_env, dense_env);
+        if (cell < 0) { kvq_set_error(KVQ_ERR_RUNTIME, "no scan kernel for seeds of %d bases at stride %d", ix->k, ix->stride); return KVQ_ERR_RUNTIME; }
+        const int si = ix->stride == 8 ? 2 : ix->stride == 4 ? 1 : 0, lg = ((cell >> 8) & 15) - 1;
+        const int k = cell & 15;
+        const bool dense = (cell & KVQ_CELL_DENSE) != 0, diag = (cell & KVQ_CELL_DIAG) != 0, stamps = (cell & KVQ_CELL_STAMPS) != 0;
+        const BpKernel *const dk = k == 5 ? kernels_k5 : k == 6 ? kernels_k6 : k == 7 ? kernels_k7 : dense ? kernels_dense : kernels_diag;
+        const BpKernel kern = diag ? dk[(lg == 2 ? 3 : 0) + si] : kernels_bp[lg == 3 ? 12 + si : lg == 1 ? 15 + si : (lg == 2 ? 6 : 0) + si + (stamps ? 3 : 0)];
+        s->kernel_cell = cell;
         hipLaunchKernelGGL(kern, dim3(grid_seeded), dim3(ST_THREADS), 0, s->stream, d_args);
     }
     if (timed) KVQ_HIP(hipEventRecord(s->ev_main.back().second, s->stream));

@@ -202,6 +202,7 @@ class Scanner(object):
         out['mutations'] = ctr[t.off_mutations:t.off_mutations + 6 * t.bases]
         path = L.kvq_scan_path(self.h)
         out['path'] = {'seeded': bool(path & 1), 'exhaustive': bool(path & 2), 'rescanned': bool(path & 4), 'tiles_rescanned': bool(path & 8)}
+        out['kernel'] = _lib.kernel_cell(L.kvq_scan_kernel(self.h))      # the scan kernel instantiation of the last seed-filter launch
         return out
 
     def hit_arrays(self):

@@ -990,6 +990,36 @@ def test_dense_table_overflows_the_candidate_queues_gracefully():
     assert (a['counters'] == b['counters']).all()
     assert len(a['hits']) > 300
     t.close()
+    # ... and the same as the oracle's
+    o = O.scan_memory(data, seqs, fold=True, **dict(cases.PRODUCT, nthreads=16))
+    assert tuple(a['hits']) == tuple(o['hits']) and a['hitseqs'] == o['hitseqs']
+    assert a['stats']['nseqhits'] == o['stats']['nseqhits'] and a['stats']['nseqbasehits'] == o['stats']['nseqbasehits']
+    assert a['stats']['readlengths'] == o['stats']['readlengths'] and a['stats']['records_parsed'] == o['stats']['records_parsed']
+    assert a['coverage'].tolist() == o['coverage'] and a['mutations'].tolist() == o['mutations']
+    if not any(os.environ.get(v) for v in ('KVQ_K', 'KVQ_STRIDE', 'KVQ_LG', 'KVQ_DENSE', 'KVQ_DBG', 'KVQ_TILE')):
+        assert a['kernel'] == dict(k=8, stride=2, lg=2, dense=True), a['kernel']
+
+
+def test_dense_table_on_300_base_reads_matches_the_oracle():
+    """the dense table (MTBC+barcodes x 8) on a text of 300-base reads: the draining kernels have no eight-lane build, the
+    general one serves the text -- same hits as the oracle"""
+    g = synth.genome()
+    seqs = synth.both_strands(synth.table(g, 'MTBC+barcodes', scale=8))
+    data = synth.reads(g, 4321, 8000, 300)
+    o = O.scan_memory(data, seqs, fold=True, **dict(cases.PRODUCT, nthreads=16))
+    assert len(o['hits']) > 300
+    t = scan.Table(seqs, **cases.PRODUCT)
+    s = scan.Scanner(t)
+    s.scan_host(data)
+    r = s.finish()
+    assert r['path'] == dict(seeded=True, exhaustive=False, rescanned=False, tiles_rescanned=False), r['path']
+    if not any(os.environ.get(v) for v in ('KVQ_K', 'KVQ_STRIDE', 'KVQ_LG', 'KVQ_DENSE', 'KVQ_DBG', 'KVQ_TILE')):
+        assert r['kernel'] == dict(k=8, stride=2, lg=-1, dense=True), r['kernel']
+    assert tuple(r['hits']) == tuple(o['hits']) and r['hitseqs'] == o['hitseqs']
+    assert r['stats']['nseqhits'] == o['stats']['nseqhits'] and r['stats']['nseqbasehits'] == o['stats']['nseqbasehits']
+    assert r['stats']['readlengths'] == o['stats']['readlengths'] and r['stats']['records_parsed'] == 8000
+    assert r['coverage'].tolist() == o['coverage'] and r['mutations'].tolist() == o['mutations']
+    s.close(); t.close()
 
 
 def test_reads_longer_than_4095_bases_keep_their_late_candidates(tmp_path):
