@@ -190,7 +190,8 @@ int32_t kvq_scan_reset(kvq_scan *s);
  * exhaustive kernels ran, bit 2 = the seed-filter pass of a batch was discarded (its speculated
  * record split failed validation, one read flooded a wave's queues) and the batch rescanned,
  * bit 3 = tiles of the seed-filter pass left their records alone (a record longer than a tile's
- * look-ahead, more newlines than its tables hold) and those records were scanned again */
+ * look-ahead, more newlines than its tables hold) and those records were scanned again, bit 4 = the text was inflated
+ * on the device (kvq_findseqs_ex, KVQ_FIND_DEVICE_INFLATE) */
 int32_t kvq_scan_path(const kvq_scan *s);
 /* 0 = let the table decide, 1 = force the exhaustive kernel for every sequence */
 void    kvq_scan_force_exhaustive(kvq_scan *s, int32_t on);
@@ -268,6 +269,16 @@ void      kvq_result_layout_words(uint64_t n, uint64_t blob_bytes, uint64_t *out
 kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
                        const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq);
 
+/* the same with options.  KVQ_FIND_DEVICE_INFLATE: when EVERY file is BGZF (bgzip) to its end (at most 10 trailing
+ * bytes), the compressed blocks are copied to the GPU, inflated there (kvq_inflate_bgzf_device), cut into the
+ * reference's chunks there and scanned where they lie; otherwise the call is kvq_findseqs.  Results, stats() and
+ * messages are kvq_findseqs's, but for one: a block that does not inflate fails with KVQ_ERR_IO "error while
+ * inflating compressed data : status=<zlib status> fpos=<stream offset of that BLOCK's first inflated byte>".
+ * kvq_scan_path bit 4 tells that the text was inflated on the device. */
+#define KVQ_FIND_DEVICE_INFLATE 1u
+kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
+                          const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags);
+
 /* destroys a scan returned by kvq_findseqs together with the table it built */
 void kvq_findseqs_free(kvq_scan *s);
 
@@ -324,6 +335,42 @@ void    kvq_synth_reads_host(uint8_t *out, int64_t first, int64_t n, int32_t L,
                              uint64_t seed, const uint8_t *genome, int64_t genome_size);
 /* i.i.d. genome bases before planting (synth.genome does the planting) */
 void    kvq_synth_genome_host(uint8_t *out, int64_t size, uint64_t seed);
+
+/* ---- BGZF (bgzip) members: raw DEFLATE, on the host and on the device -------------------------------------
+ * The reference inflates with miniz (workhorse.c:790-884); this is the library's own decoder (no zlib), the same
+ * code on both sides.  One member's payload (the bytes between its header and its CRC32/ISIZE trailer) inflates
+ * to exactly ISIZE (<= 65536) bytes or fails: status 0, -3 (Z_DATA_ERROR, not a valid DEFLATE stream) or -5
+ * (Z_BUF_ERROR, the payload ends early or the output is not exactly ISIZE bytes), -2 for bad arguments.  Bytes
+ * behind the final block are ignored; CRC32 is not checked (neither does the reference).  Reads in[0, n) and
+ * writes out[0, isize) only. */
+int32_t kvq_inflate_raw_host(const uint8_t *in, int64_t n, uint8_t *out, int64_t isize);
+
+/* host only: the blocks of the bytes of a BGZF file -- file offset, block bytes (BSIZE + 1), ISIZE -- up to cap of
+ * them; returns their number, or -1 when the bytes are not BGZF to the end (a member without the 'BC' subfield,
+ * ISIZE > 65536, more than 10 bytes behind the last block).  A member's payload is
+ * [block_off + 12 + XLEN, block_off + csize - 8). */
+int64_t kvq_bgzf_index(const uint8_t *file_bytes, int64_t n, int64_t *block_off, uint32_t *csize, uint32_t *isize, int64_t cap);
+
+/* one entry per member, in device memory: its payload at d_in + in_off (in_len bytes), its ISIZE, where its bytes go */
+typedef struct kvq_bgzf_block {
+    int64_t  in_off;
+    int64_t  out_off;
+    uint32_t in_len;
+    uint32_t isize;
+} kvq_bgzf_block;
+
+/* inflate nblocks members on the GPU (one wavefront each) into d_out; d_status[b] (device int32) gets member b's
+ * status as above.  An entry outside d_in[0, in_bytes) or d_out[0, out_bytes) gets -2 and touches nothing; a
+ * member that fails may have written part of its own output bytes, never any outside them.  Blocking; KVQ_OK or
+ * KVQ_ERR_DEVICE. */
+int32_t kvq_inflate_bgzf_device(const void *d_in, int64_t in_bytes, const kvq_bgzf_block *d_blocks, int64_t nblocks,
+                                void *d_out, int64_t out_bytes, int32_t *d_status);
+
+/* kvq_chunk_offsets for text in device memory (nbytes of it at d_data), cut on the GPU (the cuts of the device-inflate
+ * route of kvq_findseqs_ex): writes nchunks+1 offsets, so offsets holds cap + 1 entries (cap >= nbytes/512Ki + 4);
+ * returns nchunks, or -1 when a chunk holds no record start (kvq_last_error: the host route's message, offsets
+ * relative to d_data) or on a device failure */
+int64_t kvq_chunk_offsets_device(const void *d_data, int64_t nbytes, int64_t *offsets, int64_t cap);
 
 const char *kvq_version(void);
 

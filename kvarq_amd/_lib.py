@@ -90,6 +90,7 @@ PROTOTYPES = {
     'kvq_gather_host': (i32, [i32, vp, vp, vp]),
     'kvq_result_layout_words': (None, [C.c_uint64, C.c_uint64, vp]),
     'kvq_findseqs': (vp, [P(cp), i32, P(cp), P(i32), i32]),
+    'kvq_findseqs_ex': (vp, [P(cp), i32, P(cp), P(i32), i32, C.c_uint32]),
     'kvq_findseqs_free': (None, [vp]),
     'kvq_host_chunk_plan': (i64, [P(cp), i32, P(i64), P(i64), i64, P(i64), P(i64), i64]),
     'kvq_poll_stats': (None, [P(LiveStats), P(i64), P(i64), P(i64), i32]),
@@ -109,6 +110,10 @@ PROTOTYPES = {
     'kvq_synth_reads_device': (i32, [vp, i64, i64, i32, u64, vp, i64]),
     'kvq_synth_reads_host': (None, [vp, i64, i64, i32, u64, vp, i64]),
     'kvq_synth_genome_host': (None, [vp, i64, u64]),
+    'kvq_inflate_raw_host': (i32, [vp, i64, vp, i64]),
+    'kvq_bgzf_index': (i64, [vp, i64, P(i64), P(C.c_uint32), P(C.c_uint32), i64]),
+    'kvq_chunk_offsets_device': (i64, [vp, i64, P(i64), i64]),
+    'kvq_inflate_bgzf_device': (i32, [vp, i64, vp, i64, vp, i64, vp]),
     'kvq_version': (cp, []),
 }
 

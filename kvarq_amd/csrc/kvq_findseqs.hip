@@ -447,32 +447,14 @@ public:
 
 private:
     // ---- BGZF (SAM/BAM specification, section 4.1): gzip member with FEXTRA subfield 'B','C',2,0,BSIZE ----
-    struct BgzfBlock { int64_t off; uint32_t size, hdr, isize; };       // file offset, block bytes, header bytes, inflated bytes
+    typedef kvq_bgzf_entry_ BgzfBlock;                                  // file offset, block bytes, header bytes, inflated bytes
 
-    // is there a well-formed BGZF block at file offset `off`?
+    // is there a well-formed BGZF block at file offset `off`?  (the rules of kvq_bgzf_peek, which the device route walks too)
     bool bgzf_peek(int64_t off, BgzfBlock *b)
     {
-        uint8_t h[12];
         const int fdn = fileno(fd_);
-        if (off + 28 > file_size_ || pread(fdn, h, 12, (off_t)off) != 12) return false;
-        if (h[0] != 0x1F || h[1] != 0x8B || h[2] != 8 || h[3] != 4) return false;             // exactly FEXTRA, as bgzip writes
-        const uint32_t xlen = h[10] | (h[11] << 8);
-        if (xlen < 6 || xlen > 4096) return false;
-        uint8_t x[4096];
-        if (pread(fdn, x, xlen, (off_t)(off + 12)) != (ssize_t)xlen) return false;
-        uint32_t bsize = 0;
-        for (uint32_t i = 0; i + 4 <= xlen; ) {
-            const uint32_t slen = x[i + 2] | (x[i + 3] << 8);
-            if (x[i] == 'B' && x[i + 1] == 'C' && slen == 2 && i + 6 <= xlen) bsize = (x[i + 4] | (x[i + 5] << 8)) + 1u;
-            i += 4 + slen;
-        }
-        const uint32_t hdr = 12 + xlen;
-        if (bsize < hdr + 8 || off + bsize > file_size_) return false;
-        uint8_t t[4];
-        if (pread(fdn, t, 4, (off_t)(off + bsize - 4)) != 4) return false;
-        b->off = off; b->size = bsize; b->hdr = hdr;
-        b->isize = t[0] | (t[1] << 8) | (t[2] << 16) | ((uint32_t)t[3] << 24);
-        return b->isize <= 65536;
+        auto read = [&](uint8_t *dst, int64_t k, int64_t at) -> int64_t { const ssize_t got = pread(fdn, dst, (size_t)k, (off_t)at); return got < 0 ? 0 : (int64_t)got; };
+        return kvq_bgzf_peek(read, file_size_, off, b);
     }
 
     // inflate as many whole BGZF blocks as fit into cap bytes, nthreads workers; -2 = hand over to the serial path
@@ -711,7 +693,13 @@ struct ScanSink {
     // lengths and hits per sequence of different batches in one answer.)
     int64_t *snap = nullptr; size_t snap_cap = 0, head = 0; hipEvent_t snap_ev = nullptr;
     bool snap_pending = false; int64_t snap_parsed = 0, enq_parsed = 0, last_parsed = 0;
-    ~ScanSink() { if (snap_ev) (void)hipEventDestroy(snap_ev); if (snap) pinned_give(snap, snap_cap); }
+    bool staged = false;               // batches are device text of the device-inflate route (kvq_scan_staged), not host buffers
+    ~ScanSink()
+    {
+        if (s && s->stream) (void)hipStreamSynchronize(s->stream);          // (the snapshot copy may still be on its way into snap)
+        if (snap_ev) (void)hipEventDestroy(snap_ev);
+        if (snap) pinned_give(snap, snap_cap);
+    }
     void begin(int64_t total)
     {
         live_reset(s->t->nseq, total);
@@ -732,12 +720,14 @@ struct ScanSink {
         }
         // hand this batch over (its text sets out at once, the kernels of the batch before it are enqueued: kvq_scan_host_async) and
         // return, so that the reader fills the other host buffer while this one crosses PCIe
-        const int rc = kvq_scan_host_async(s, data, nbytes, off, nchunks, fpos);
+        const int rc = staged ? kvq_scan_staged(s, data, nbytes, off, nchunks, fpos) : kvq_scan_host_async(s, data, nbytes, off, nchunks, fpos);
         if (rc) return rc;
-        // the stream now holds the kernels of every batch up to the one handed over in the call before this: snapshot behind them
-        if (snap && snap_ev && last_parsed > 0) {
+        // the stream now holds the kernels of every batch up to the one handed over in the call before this -- up to this one for
+        // staged text, whose kernels kvq_scan_staged enqueues at once: snapshot behind them, with the byte count that belongs to it
+        const int64_t behind = staged ? parsed : last_parsed;
+        if (snap && snap_ev && behind > 0) {
             if (hipMemcpyAsync(snap, s->d_ctr, head * 8, hipMemcpyDeviceToHost, s->stream) == hipSuccess && hipEventRecord(snap_ev, s->stream) == hipSuccess) {
-                snap_pending = true; snap_parsed = last_parsed;
+                snap_pending = true; snap_parsed = behind;
             } else (void)hipGetLastError();
         }
         last_parsed = parsed;
@@ -745,13 +735,216 @@ struct ScanSink {
     }
 };
 
-// one pass over the files with the current arena; KVQ_NEED_RESCAN asks for another
-static int findseqs_pass(kvq_scan *s, const char *const *files, int nfiles, uint8_t *pin, uint8_t *pin2, int64_t pin_cap)
+// ---------------------------------------------------------------------------
+// the device-inflate route (kvq_findseqs_ex with KVQ_FIND_DEVICE_INFLATE)
+// ---------------------------------------------------------------------------
+
+struct BgzfFile { std::string name; int64_t size = 0; std::vector<kvq_bgzf_entry_> blocks; };
+
+// is every file a ".gz" (the host reader decides by suffix) that is BGZF to its end?  Its blocks, walked with the host
+// reader's acceptance rules (bgzf_peek)
+static bool bgzf_files(const char *const *files, int nfiles, std::vector<BgzfFile> &out)
 {
-    ScanSink sink; sink.s = s;
+    out.clear();
+    for (int i = 0; i < nfiles; i++) {
+        BgzfFile f; f.name = files[i];
+        if (!(f.name.size() >= 3 && f.name.compare(f.name.size() - 3, 3, ".gz") == 0)) return false;
+        FILE *fd = fopen(f.name.c_str(), "rb");
+        if (!fd) return false;
+        fseek(fd, 0, SEEK_END); f.size = ftell(fd);
+        const int fdn = fileno(fd);
+        auto read = [&](uint8_t *dst, int64_t k, int64_t at) -> int64_t { const ssize_t got = pread(fdn, dst, (size_t)k, (off_t)at); return got < 0 ? 0 : (int64_t)got; };
+        const bool ok = kvq_bgzf_walk(read, f.size, f.blocks);
+        fclose(fd);
+        if (!ok) return false;
+        out.push_back(std::move(f));
+    }
+    return nfiles > 0;
+}
+
+// bytes [at, at + n) of a file into dst, by up to `nthreads` preads at once
+static bool pread_run(int fdn, uint8_t *dst, int64_t n, int64_t at, int nthreads)
+{
+    int nt = nthreads < 1 ? 1 : (nthreads > 16 ? 16 : nthreads);
+    if (n < (4 << 20)) nt = 1;
+    std::atomic<int> bad{0};
+    auto slice = [&](int t) {
+        int64_t a = n * t / nt, b = n * (t + 1) / nt;
+        while (a < b) {
+            const ssize_t got = pread(fdn, dst + a, (size_t)(b - a), (off_t)(at + a));
+            if (got <= 0) { bad = 1; return; }
+            a += got;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(slice, t);
+    slice(0);
+    for (auto &x : th) x.join();
+    return !bad.load();
+}
+
+static int pinned_grow(void **p, size_t *cap, size_t need)
+{
+    if (*cap >= need) return KVQ_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t want = need + need / 4;
+    if (hipHostMalloc(p, want, hipHostMallocDefault) != hipSuccess) { *p = nullptr; kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for scanning"); return KVQ_ERR_MEMORY; }
+    *cap = want;
+    return KVQ_OK;
+}
+
+// buffers of the route, kept from call to call (one findseqs runs at a time): per slot the compressed run and its block
+// table in pinned and in device memory, the statuses, the inflated text; the cut results
+static struct DevRoute {
+    void *pin[2] = { nullptr, nullptr }, *ptab[2] = { nullptr, nullptr }, *pstat[2] = { nullptr, nullptr }, *pcut = nullptr;
+    size_t pin_cap[2] = { 0, 0 }, ptab_cap[2] = { 0, 0 }, pstat_cap[2] = { 0, 0 }, pcut_cap = 0;
+    DevBuf d_comp[2], d_tab[2], d_stat[2], d_text[2], d_cut;
+} g_dev;
+
+// inflated bytes per device batch: 256 MiB, about 4 100 blocks of bgzip's 65 280 bytes (KVQ_INFLATE_BATCH_MB=<2..1024>)
+static int64_t device_batch_bytes()
+{
+    const char *e = getenv("KVQ_INFLATE_BATCH_MB");
+    const long v = e ? atol(e) : 0;
+    return (int64_t)(v >= 2 && v <= 1024 ? v : 256) << 20;
+}
+
+// The walk of stream_batches for files that are BGZF to the end, with the inflate and the cuts on the GPU.  Per batch: a run of
+// whole blocks is read into pinned memory (the next run is read while the GPU inflates this one), copied to the device and
+// inflated behind the unfinished chunk the batch before left (copied device to device to the front of the text buffer, so that
+// the batch starts 16-byte aligned); kvq_cut_chunks cuts the chunks, their offsets come back to the host, and the text is
+// handed to the scan where it lies.  The two text buffers alternate after every batch handed to the scan (and only then: a run
+// that hands over nothing -- an empty file -- must not overwrite the text of the batch in flight, which may still be scanned
+// again from where it lies); the scan's stream runs a batch's kernels before the inflate of the batch after the next one.
+template <class Sink>
+static int stream_device(Sink &sink, kvq_scan *s, const std::vector<BgzfFile> &files, int64_t *parsed, int64_t *total_out)
+{
+    int rc;
+    int64_t size_all = 0;
+    for (auto &f : files) size_all += f.size;
+    sink.begin(size_all);
+    const int64_t batch_cap = device_batch_bytes(), text_cap = batch_cap + KVQ_SCANBUFSIZE + 64;
+    for (int i = 0; i < 2; i++) if ((rc = g_dev.d_text[i].ensure((size_t)text_cap))) return rc;
+    if ((rc = g_dev.d_cut.ensure((8 + KVQ_CUT_CAP) * 8))) return rc;
+    if ((rc = pinned_grow(&g_dev.pcut, &g_dev.pcut_cap, (8 + KVQ_CUT_CAP) * 8))) return rc;
+    kvq_config cfg; kvq_config_get(&cfg);
+    hipStream_t st = s->stream;
+
+    struct Run { size_t f = 0, b0 = 0, b1 = 0; int64_t c0 = 0, c1 = 0, isz = 0; bool eof = false, valid = false; };
+    auto next_run = [&](size_t f, size_t b0) {
+        Run r; r.f = f; r.b0 = b0; r.b1 = b0; r.valid = true;
+        const auto &bl = files[f].blocks;
+        while (r.b1 < bl.size() && (r.b1 == b0 || r.isz + bl[r.b1].isize <= batch_cap)) r.isz += bl[r.b1++].isize;
+        r.c0 = bl[b0].off; r.c1 = bl[r.b1 - 1].off + bl[r.b1 - 1].size; r.eof = r.b1 == bl.size();
+        return r;
+    };
+    FILE *fd = nullptr; size_t fd_of = (size_t)-1;
+    struct Closer { FILE *&f; ~Closer() { if (f) fclose(f); } } closer{ fd };
+    auto read_run = [&](const Run &r, int slot) -> int {
+        if (fd_of != r.f) {
+            if (fd) fclose(fd);
+            fd = fopen(files[r.f].name.c_str(), "rb"); fd_of = r.f;
+            if (!fd) { kvq_set_error(KVQ_ERR_IO, "cannot open file"); return KVQ_ERR_IO; }
+        }
+        int rc2 = pinned_grow(&g_dev.pin[slot], &g_dev.pin_cap[slot], (size_t)(r.c1 - r.c0));
+        if (rc2) return rc2;
+        if (!pread_run(fileno(fd), (uint8_t *)g_dev.pin[slot], r.c1 - r.c0, r.c0, cfg.nthreads)) {
+            kvq_set_error(KVQ_ERR_IO, "could not read enough bytes from .fastq.gz : I/O error"); return KVQ_ERR_IO;
+        }
+        return KVQ_OK;
+    };
+
+    int64_t fpos = 0, ftell0 = 0, consumed = 0, total = size_all;
+    int64_t carry = 0, carry_src = 0, fill = 0, text_fpos = 0;       // the unfinished chunk of the file, where it lies (text buffer cb)
+    int tb = 0, cb = 0;                                               // the text buffer of this run
+    Run cur = next_run(0, 0);
+    if ((rc = read_run(cur, 0))) return rc;
+    for (int k = 0; cur.valid && !g_stop.load(); k++) {
+        const int slot = k & 1;
+        const auto &bl = files[cur.f].blocks;
+        const int64_t nb = (int64_t)(cur.b1 - cur.b0);
+        if ((rc = pinned_grow(&g_dev.ptab[slot], &g_dev.ptab_cap[slot], (size_t)nb * sizeof(kvq_bgzf_block)))) return rc;
+        if ((rc = pinned_grow(&g_dev.pstat[slot], &g_dev.pstat_cap[slot], (size_t)nb * 4))) return rc;
+        kvq_bgzf_block *tab = (kvq_bgzf_block *)g_dev.ptab[slot];
+        int64_t o = carry;
+        for (int64_t i = 0; i < nb; i++) {
+            const kvq_bgzf_entry_ &b = bl[cur.b0 + i];
+            tab[i].in_off = b.off - cur.c0 + b.hdr; tab[i].in_len = b.size - b.hdr - 8; tab[i].isize = b.isize; tab[i].out_off = o;
+            o += b.isize;
+        }
+        const int64_t have = o;
+        if ((rc = g_dev.d_comp[slot].ensure((size_t)(cur.c1 - cur.c0)))) return rc;
+        if ((rc = g_dev.d_tab[slot].ensure((size_t)nb * sizeof(kvq_bgzf_block)))) return rc;
+        if ((rc = g_dev.d_stat[slot].ensure((size_t)nb * 4))) return rc;
+        uint8_t *text = g_dev.d_text[tb].as<uint8_t>();
+        KVQ_HIP(hipMemcpyAsync(g_dev.d_comp[slot].p, g_dev.pin[slot], (size_t)(cur.c1 - cur.c0), hipMemcpyHostToDevice, st));
+        KVQ_HIP(hipMemcpyAsync(g_dev.d_tab[slot].p, tab, (size_t)nb * sizeof(kvq_bgzf_block), hipMemcpyHostToDevice, st));
+        const uint8_t *carry_at = g_dev.d_text[cb].as<uint8_t>() + carry_src;
+        if (carry && carry_at != text) KVQ_HIP(hipMemcpyAsync(text, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, st));
+        if ((rc = kvq_inflate_bgzf_launch(g_dev.d_comp[slot].as<uint8_t>(), cur.c1 - cur.c0, g_dev.d_tab[slot].as<kvq_bgzf_block>(), nb,
+                                          text, text_cap, g_dev.d_stat[slot].as<int32_t>(), st))) return rc;
+        KVQ_HIP(hipMemcpyAsync(g_dev.pstat[slot], g_dev.d_stat[slot].p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        int64_t *cut = (int64_t *)g_dev.pcut;
+        int64_t *d_cut = g_dev.d_cut.as<int64_t>();
+        if ((rc = kvq_cut_chunks_launch(text, have, 0, fill, d_cut + 8, KVQ_CUT_CAP, d_cut, st))) return rc;
+        KVQ_HIP(hipMemcpyAsync(cut, d_cut, (8 + KVQ_CUT_CAP) * 8, hipMemcpyDeviceToHost, st));
+        // the next run is read while the GPU works on this one
+        Run nxt;
+        if (!cur.eof) nxt = next_run(cur.f, cur.b1);
+        else if (cur.f + 1 < files.size()) nxt = next_run(cur.f + 1, 0);
+        if (nxt.valid && (rc = read_run(nxt, slot ^ 1))) return rc;
+        KVQ_HIP(hipStreamSynchronize(st));
+        const int32_t *stat = (const int32_t *)g_dev.pstat[slot];
+        for (int64_t i = 0; i < nb; i++)
+            if (stat[i] != 0) {
+                kvq_set_error(KVQ_ERR_IO, "error while inflating compressed data : status=%d fpos=%ld", stat[i], (long)(text_fpos + tab[i].out_off));
+                return KVQ_ERR_IO;
+            }
+        std::vector<int64_t> off;
+        for (;;) {
+            if (cut[3]) {
+                kvq_set_error(KVQ_ERR_RUNTIME, "could find beginning of record; read %ld bytes up to %ld", (long)cut[4], (long)(text_fpos + cut[5]));
+                return KVQ_ERR_RUNTIME;
+            }
+            off.insert(off.end(), cut + 8, cut + 8 + cut[0]);
+            if (cut[0] < KVQ_CUT_CAP) break;
+            if ((rc = kvq_cut_chunks_launch(text, have, cut[1], cut[2], d_cut + 8, KVQ_CUT_CAP, d_cut, st))) return rc;
+            KVQ_HIP(hipMemcpyAsync(cut, d_cut, (8 + KVQ_CUT_CAP) * 8, hipMemcpyDeviceToHost, st));
+            KVQ_HIP(hipStreamSynchronize(st));
+        }
+        int64_t cs = cut[1];
+        fill = cut[2];
+        consumed += cur.c1 - cur.c0;
+        if (cur.eof) consumed += files[cur.f].size - cur.c1;                // (the trailer behind the last block)
+        fpos += cur.isz;
+        if (ftell0 + consumed > 0)
+            total = (int64_t)(size_t)((float)size_all * fpos / (ftell0 + consumed));          // the host reader's estimate (read_bgzf)
+        if (cur.eof) { if (have > cs) off.push_back(cs); cs = have; }
+        const bool handed = !off.empty();
+        if (handed) {
+            off.push_back(cs);
+            if ((rc = sink.batch(text, cs, off.data(), (int64_t)off.size() - 1, text_fpos, fpos, total))) return rc;
+        }
+        if (cur.eof) { ftell0 += consumed; consumed = 0; carry = 0; fill = 0; text_fpos = fpos; }
+        else { carry = have - cs; carry_src = cs; cb = tb; fill -= cs; text_fpos += cs; }
+        if (handed) tb ^= 1;
+        cur = nxt;
+    }
+    *parsed = fpos; *total_out = total;
+    return KVQ_OK;
+}
+
+// one pass over the files with the current arena; KVQ_NEED_RESCAN asks for another.  bz: the files' BGZF blocks when the
+// device-inflate route was taken
+static int findseqs_pass(kvq_scan *s, const char *const *files, int nfiles, uint8_t *pin, uint8_t *pin2, int64_t pin_cap,
+                         const std::vector<BgzfFile> *bz = nullptr)
+{
+    ScanSink sink; sink.s = s; sink.staged = bz != nullptr;
     int64_t parsed = 0, total = 0;
     const double tp0 = now_ms();
-    int rc = stream_batches(sink, files, nfiles, pin, pin_cap, &parsed, &total, pin2);                 // two host buffers
+    int rc = bz ? stream_device(sink, s, *bz, &parsed, &total)
+                : stream_batches(sink, files, nfiles, pin, pin_cap, &parsed, &total, pin2);                 // two host buffers
     if (g_timing) fprintf(stderr, "findseqs pass: stream %.1f ms\n", now_ms() - tp0);
     if (rc) return rc;
     s->parsed = parsed; s->total = total;
@@ -790,8 +983,8 @@ extern "C" int64_t kvq_host_chunk_plan(const char *const *files, int32_t nfiles,
     return rc ? -1 : sink.n;
 }
 
-extern "C" kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
-                                  const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq)
+static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
+                               const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags)
 {
     kvq_clear_error();
     int expected = 0;
@@ -831,7 +1024,10 @@ extern "C" kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
     // streaming a 1 GB file through them (only one findseqs runs at a time, g_running)
     static uint8_t *g_pin = nullptr;
     const int64_t pin_cap = BATCH_BYTES + 2 * KVQ_SCANBUFSIZE;
-    if (s && !g_pin && hipHostMalloc((void **)&g_pin, (size_t)pin_cap * 2, hipHostMallocDefault) != hipSuccess) {
+    // the device-inflate route: asked for, and every file is BGZF to its end (else the call takes the host route unchanged)
+    std::vector<BgzfFile> bz;
+    const bool dev = s && (flags & KVQ_FIND_DEVICE_INFLATE) && bgzf_files(files, nfiles, bz);
+    if (s && !dev && !g_pin && hipHostMalloc((void **)&g_pin, (size_t)pin_cap * 2, hipHostMallocDefault) != hipSuccess) {
         kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for scanning"); g_pin = nullptr;
     }
     uint8_t *const pin = g_pin;
@@ -842,9 +1038,10 @@ extern "C" kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
         if (v >= 2 && (v << 20) < BATCH_BYTES) use_cap = ((int64_t)v << 20) + 2 * KVQ_SCANBUFSIZE;
     }
     const double tf2 = now_ms();
-    if (s && pin) {
+    if (s && (pin || dev)) {
         for (int attempt = 0; attempt < 4; attempt++) {
-            const int rc = findseqs_pass(s, files, nfiles, pin, pin + pin_cap, use_cap);
+            const int rc = dev ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, &bz)
+                               : findseqs_pass(s, files, nfiles, pin, pin + pin_cap, use_cap);
             if (rc != KVQ_NEED_RESCAN) break;
             // the hit arena was too small (it has been enlarged): scan again from the start
             if (kvq_scan_reset(s)) break;
@@ -854,10 +1051,23 @@ extern "C" kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
     const double tf3 = now_ms();
     if (s && s->stream) (void)hipStreamSynchronize(s->stream);        // nothing may still be reading the host buffers
     if (g_timing) fprintf(stderr, "findseqs: table+scan %.1f  pinned alloc %.1f  passes %.1f  free %.1f ms\n", tf1 - tf0, tf2 - tf1, tf3 - tf2, now_ms() - tf3);
+    if (s && dev) s->path_bits |= 16;                                 // (kvq_scan_path bit 4: the text was inflated on the device)
     g_running = 0;
     if (s) s->t = t;          // the scan owns its table: destroyed with it (kvq_findseqs_free)
     else if (t) kvq_table_destroy(t);
     return s;
+}
+
+extern "C" kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
+                                  const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq)
+{
+    return findseqs_impl(files, nfiles, seqs, seqlens, nseq, 0);
+}
+
+extern "C" kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
+                                     const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags)
+{
+    return findseqs_impl(files, nfiles, seqs, seqlens, nseq, flags);
 }
 
 // destroy a scan returned by kvq_findseqs together with the table it created
@@ -874,3 +1084,4 @@ extern "C" void kvq_findseqs_free(kvq_scan *s)
     kvq_scan_destroy(s);
     kvq_table_destroy(t);
 }
+

@@ -70,6 +70,7 @@ struct Batch {
     bool skips_done = false;  // its skipped tiles have been scanned again
     size_t skip_at = 0;       // its list of skipped tiles in the table pool
     uint32_t tile_bytes = 0;  // bytes a tile owned when it was scanned
+    const uint8_t *staged = nullptr;   // device text owned by the caller while the batch is in flight (kvq_scan_staged): a host batch for every other purpose
 };
 
 struct kvq_comm;
@@ -182,3 +183,14 @@ int32_t  kvq_scan_pick(int k, int stride, bool ix_dense, uint32_t rec_bytes, uin
 
 // synth.hip
 // (C ABI only)
+
+// kvq_runtime.hip: a batch whose text the CALLER has put into device memory and keeps there only until the next batch
+// is handed over (the device-inflate route of findseqs): scanned, settled and -- on a hit-arena overflow -- fed again
+// like a host batch, never replayed from its buffer
+int kvq_scan_staged(kvq_scan *s, const uint8_t *d_text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t fpos_base);
+
+// kernels_inflate.hip
+struct kvq_bgzf_entry_ { int64_t off; uint32_t size, hdr, isize; };     // a BGZF block of a file: offset, bytes, header bytes, inflated bytes
+int kvq_inflate_bgzf_launch(const uint8_t *d_in, int64_t in_bytes, const kvq_bgzf_block *d_tab, int64_t nblocks,
+                            uint8_t *d_out, int64_t out_bytes, int32_t *d_status, hipStream_t stream);
+int kvq_cut_chunks_launch(const uint8_t *d_text, int64_t have, int64_t cs, int64_t fill, int64_t *d_offs, int64_t cap, int64_t *d_res, hipStream_t stream);

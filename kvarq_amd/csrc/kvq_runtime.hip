@@ -737,7 +737,7 @@ static int settle_in_flight(kvq_scan *s)
     Batch again = s->batches[b]; again.is_redo = true;
     s->batches.push_back(again);
     s->path_bits |= 4;
-    int rc = run_batch(s, stage_of(s, s->run_slot).as<uint8_t>(), again.nbytes, again.chunk_off.data(), (int64_t)again.chunk_off.size() - 1,
+    int rc = run_batch(s, again.staged ? again.staged : stage_of(s, s->run_slot).as<uint8_t>(), again.nbytes, again.chunk_off.data(), (int64_t)again.chunk_off.size() - 1,
                        again.fpos_base, s->batches.size() - 1, true);
     if (rc) return rc;
     KVQ_HIP(hipStreamSynchronize(s->stream));
@@ -800,6 +800,36 @@ extern "C" int32_t kvq_scan_host_async(kvq_scan *s, const void *h_data, int64_t 
     s->parsed += nbytes; s->total += nbytes;
     // (a caller that alternates two host buffers writes next into the one of the call before: that text has left it)
     if (s->host_pending >= 0) KVQ_HIP(hipEventSynchronize(s->ev_copy[s->run_slot]));
+    return KVQ_OK;
+}
+
+// a batch already in device memory that the caller reuses once the next batch is handed over (kvq_host.h)
+int kvq_scan_staged(kvq_scan *s, const uint8_t *d_text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t fpos_base)
+{
+    kvq_clear_error();
+    if (nbytes <= 0 || nchunks <= 0) return KVQ_OK;
+    int rc;
+    if ((rc = check_batch(d_text, nbytes, chunk_off, nchunks, s->batches.size() + (s->copied_pending ? 1u : 0u), true))) return rc;
+    if ((rc = settle_in_flight(s))) return rc;                     // (the batch before: its text is still where the caller put it)
+    if ((rc = launch_copied(s))) return rc;
+    if (s->tile_bytes == 0) {                                      // size the seed-filter tiles from the head of the text
+        std::vector<uint8_t> head((size_t)std::min<int64_t>(nbytes, 128 << 10));
+        KVQ_HIP(hipMemcpyAsync(head.data(), d_text, head.size(), hipMemcpyDeviceToHost, s->stream));
+        KVQ_HIP(hipStreamSynchronize(s->stream));
+        s->tile_bytes = kvq_tile_for_text(head.data(), head.size(), &s->rec_bytes);
+    }
+    s->pool.used = 0;
+    *reinterpret_cast<unsigned int *>(s->pin_small + 40) = 0;
+    Batch b; b.d_data = nullptr; b.staged = d_text; b.nbytes = nbytes; b.fpos_base = fpos_base;
+    b.chunk_off.assign(chunk_off, chunk_off + nchunks + 1);
+    s->batches.push_back(b);
+    s->host_batches = true;
+    s->parsed += nbytes; s->total += nbytes;
+    rc = run_batch(s, d_text, nbytes, chunk_off, nchunks, fpos_base, s->batches.size() - 1, false);
+    if (rc) return rc;
+    if (s->path_bits & 1)
+        KVQ_HIP(hipMemcpyAsync(s->pin_small + 40, s->d_fail + (s->batches.size() - 1), 4, hipMemcpyDeviceToHost, s->stream));
+    s->host_pending = (int64_t)s->batches.size() - 1;
     return KVQ_OK;
 }
 

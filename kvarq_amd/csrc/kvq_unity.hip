@@ -7,5 +7,6 @@
 #include "kernels_results.hip"
 #include "synth.hip"
 #include "kvq_runtime.hip"
+#include "kernels_inflate.hip"
 #include "kvq_findseqs.hip"
 #include "kvq_dist.hip"

@@ -105,14 +105,27 @@ def _stats_dict(readlengths, longest, nseqbasehits, nseqhits, parsed, total, sig
     }
 
 
-def findseqs(fname, sequences):
+_last_inflate = None
+INFLATE_FLAGS = {'host': 0, 'device': 1}           # KVQ_FIND_DEVICE_INFLATE
+PATH_DEVICE_INFLATE = 0x10                         # kvq_scan_path bit 4
+
+
+def findseqs(fname, sequences, *, inflate='host'):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
     fname: file name or sequence of file names (plain or ``.gz``), scanned as one
     stream; sequences: sequence of strings.  Returns ``{'hits': tuple of Hit,
-    'stats': dict as stats(), 'hitseqs': list of hit base strings}``."""
+    'stats': dict as stats(), 'hitseqs': list of hit base strings}``.
+
+    inflate='device' (not in the reference): when every file is BGZF (bgzip) to its
+    end, the compressed blocks go to the GPU and are inflated, cut and scanned there;
+    otherwise the call is the default one.  last_inflate() tells which route ran."""
     import os, time
+    global _last_inflate
+    if inflate not in INFLATE_FLAGS:
+        raise ValueError("inflate must be 'host' or 'device'")
+    _last_inflate = None
     t_in = time.perf_counter()
     L = _lib.lib()
     if isinstance(fname, (str, bytes)):
@@ -148,9 +161,14 @@ def findseqs(fname, sequences):
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
-    h = L.kvq_findseqs(farr, len(bfiles), sarr, lens, n)
+    if inflate == 'host':
+        h = L.kvq_findseqs(farr, len(bfiles), sarr, lens, n)
+    else:
+        h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate])
     t_1 = time.perf_counter()
     try:
+        if h:
+            _last_inflate = 'device' if L.kvq_scan_path(h) & PATH_DEVICE_INFLATE else 'host'
         code, _ = _lib.last_error()
         if not h or code:
             _raise_last()
@@ -186,6 +204,12 @@ def findseqs(fname, sequences):
             if os.environ.get('KVQ_TIMING'):
                 import sys
                 sys.stderr.write('engine.findseqs: free %.1f ms\n' % ((time.perf_counter() - t_f) * 1e3))
+
+
+def last_inflate():
+    """where the text of the last findseqs call was inflated: 'device' (the BGZF route on the
+    GPU), 'host' (the reader on the CPU, plain files included), or None before any call"""
+    return _last_inflate
 
 
 def _sigints():

@@ -276,3 +276,12 @@ class DeviceBuffer(object):
             self.free()
         except Exception:
             pass
+
+
+def inflate_bgzf_device(d_in, in_bytes, d_blocks, nblocks, d_out, out_bytes, d_status):
+    """kvq_inflate_bgzf_device: inflate the BGZF members of a block table in device memory
+    (kvq_bgzf_block entries: payload offset, output offset, payload bytes, isize) into d_out;
+    d_status (device int32 per member) gets 0, -3 or -5 (zlib's codes).  Pointers are device
+    addresses as ints (e.g. torch tensors' data_ptr()).  Blocks until done."""
+    _check(_lib.lib().kvq_inflate_bgzf_device(C.c_void_p(d_in), in_bytes, C.c_void_p(d_blocks), nblocks,
+                                               C.c_void_p(d_out), out_bytes, C.c_void_p(d_status)))
