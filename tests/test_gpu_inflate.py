@@ -25,24 +25,37 @@ BLOCK = np.dtype([('in_off', '<i8'), ('out_off', '<i8'), ('in_len', '<u4'), ('is
 
 
 def _inflate_on_device(members, fill=0xAB):
-    """members: [(payload, isize)] -> (statuses, [bytes of each member's output slot])"""
+    """members: [(payload, isize)] -> (statuses, [bytes of each member's output slot]).  Slot i is followed by a gap of
+    i % 13 bytes (slots at every alignment) filled with `fill`; asserts that no member wrote into a gap, failing or not"""
     comp = b''.join(p for p, _ in members)
-    tab = np.zeros(len(members), BLOCK)
-    a = o = 0
-    for i, (p, isize) in enumerate(members):
-        tab[i] = (a, o, len(p), isize)
-        a += len(p); o += isize + (i % 13)                    # (slots at every alignment)
+    n = len(members)
+    in_len = np.array([len(p) for p, _ in members], np.int64)
+    isize = np.array([i for _, i in members], np.int64)
+    span = isize + np.arange(n, dtype=np.int64) % 13
+    tab = np.zeros(n, BLOCK)
+    tab['in_off'] = np.cumsum(in_len) - in_len
+    tab['out_off'] = np.cumsum(span) - span
+    tab['in_len'] = in_len
+    tab['isize'] = isize
+    o = int(span.sum())
     d_in, d_tab = scan.DeviceBuffer(max(1, len(comp))), scan.DeviceBuffer(tab.nbytes)
-    d_out, d_st = scan.DeviceBuffer(max(1, o)), scan.DeviceBuffer(4 * len(members))
+    d_out, d_st = scan.DeviceBuffer(max(1, o)), scan.DeviceBuffer(4 * n)
     d_in.upload(np.frombuffer(comp, np.uint8)) if comp else None
     d_tab.upload(tab.view(np.uint8))
     d_out.upload(np.full(max(1, o), fill, np.uint8))
-    scan.inflate_bgzf_device(d_in.ptr, len(comp), d_tab.ptr, len(members), d_out.ptr, o, d_st.ptr)
-    out = d_out.download().tobytes()
-    st = d_st.download().view(np.int32).tolist()
+    scan.inflate_bgzf_device(d_in.ptr, len(comp), d_tab.ptr, n, d_out.ptr, o, d_st.ptr)
+    out = d_out.download()[:o]
+    st = d_st.download().view(np.int32)[:n].tolist()
     for d in (d_in, d_tab, d_out, d_st):
         d.free()
-    return st, [out[int(t['out_off']):int(t['out_off']) + int(t['isize'])] for t in tab]
+    edge = np.zeros(o + 1, np.int64)                           # +1 over each slot, 0 over the gaps
+    np.add.at(edge, tab['out_off'], 1)
+    np.add.at(edge, tab['out_off'] + isize, -1)
+    gap = np.cumsum(edge[:o]) == 0
+    bad = np.flatnonzero(gap & (out != fill))
+    assert bad.size == 0, 'member output outside its slot at byte %d' % bad[0]
+    out = out.tobytes()
+    return st, [out[int(a):int(a) + int(b)] for a, b in zip(tab['out_off'], isize)]
 
 
 def test_inflate_kernel_equals_zlib_on_the_valid_corpus():
@@ -80,6 +93,73 @@ def test_entries_outside_the_buffers_are_refused():
     scan.inflate_bgzf_device(d_in.ptr, len(p), d_tab.ptr, 2, d_out.ptr, 16, d_st.ptr)
     assert d_st.download().view(np.int32).tolist() == [0, -2]
     assert d_out.download()[:15].tobytes() == b'@r\nACGT\n+\nIIII\n'
+
+
+EDGE_VALID = IC.edge_valid()
+EDGE_INVALID = IC.edge_invalid()
+
+
+def test_inflate_kernel_on_the_structured_corpus():
+    """the writer-made edges: distances up to the ring's 32 KiB, copies and stored blocks across its wrap, zlib's
+    rules at the edges of the Huffman headers; statuses equal to the host decoder's, bytes equal to zlib's"""
+    members = [(p, len(t)) for _, p, t, _ in EDGE_VALID] + [(p, isize) for _, p, isize, _ in EDGE_INVALID]
+    want = [B.inflate_raw_host(p, isize)[0] for p, isize in members]
+    st, got = _inflate_on_device(members)
+    names = [m[0] for m in EDGE_VALID] + [m[0] for m in EDGE_INVALID]
+    assert list(zip(names, st)) == list(zip(names, want))
+    for (name, p, t, _), s, g in zip(EDGE_VALID, st, got):
+        assert s == 0, name
+        assert g == t == IC.zlib_verdict(p, len(t))[1], name
+    assert all(s < 0 for s in st[len(EDGE_VALID):])
+
+
+def test_inflate_kernel_second_member_of_a_workgroup():
+    """the grid stops at 2^20 workgroups: a workgroup decodes member b and then member b + 2^20 over the ring and the
+    tables b left.  The head holds the corpus reversed, then empty members (03 00, isize 0); the tail the corpus"""
+    corpus = [(p, len(t)) for _, p, t, _ in EDGE_VALID] + [(p, isize) for _, p, isize, _ in EDGE_INVALID]
+    k = len(corpus)
+    members = corpus[::-1] + [(b'\x03\x00', 0)] * ((1 << 20) - k) + corpus
+    want = [B.inflate_raw_host(p, isize)[0] for p, isize in corpus]
+    st, got = _inflate_on_device(members)
+    assert want[:len(EDGE_VALID)] == [0] * len(EDGE_VALID)
+    assert st[:k] == want[::-1]
+    assert not any(st[k:1 << 20]) and all(g == b'' for g in got[k:1 << 20])
+    assert st[1 << 20:] == want
+    for (p, isize), s, g in zip(corpus, st[1 << 20:], got[1 << 20:]):
+        if s == 0:
+            assert g == IC.zlib_verdict(p, isize)[1]
+
+
+def test_inflate_kernel_on_libdeflate_members():
+    corpus = IC.libdeflate_corpus()
+    if corpus is None:
+        pytest.skip('libdeflate does not load on this machine')
+    st, got = _inflate_on_device([(p, len(t)) for _, p, t in corpus])
+    for (label, _, t), s, g in zip(corpus, st, got):
+        assert (s, g) == (0, t), label
+
+
+def test_device_route_on_a_writer_made_bgzf_file(tmp_path):
+    """FastQ text whose members copy from as far back as the 32 KiB window allows (distance 32 768 included):
+    the device route equals the host route (zlib) and the oracle, hits in order, counters and stats"""
+    t = cases.ragged(11, 2500, cases.RAGGED_TARGETS, maxlen=500)           # two 1 MiB chunks
+    z, far = IC.writer_bgzf(t)
+    assert far == 32768 and gzip.decompress(z) == t
+    p = str(tmp_path / 'far.fastq.gz')
+    open(p, 'wb').write(z)
+    cfg = dict(cases.PRODUCT, nthreads=4)
+    engine.config(**cfg)
+    host, dev = _both([p], cases.RAGGED_SEQS)
+    assert dev[0] == 'ok' and len(dev[1]) > 0
+    assert dev == host
+    o = O.findseqs([p], cases.RAGGED_SEQS, **cfg)
+    assert tuple(dev[1]) == tuple(o['hits'])
+    assert [bytes(h) for h in dev[2]] == o['hitseqs']
+    assert dev[3] == o['stats']
+    dev_flag, dev_ctr = _counters([p], cases.RAGGED_SEQS, engine.INFLATE_FLAGS['device'])
+    host_flag, host_ctr = _counters([p], cases.RAGGED_SEQS, engine.INFLATE_FLAGS['host'])
+    assert dev_flag and not host_flag
+    assert dev_ctr.sum() > 0 and (dev_ctr == host_ctr).all()
 
 
 def _device_cuts(text):

@@ -2,22 +2,39 @@
 CPU checks of the library's raw-DEFLATE decoder (kvarq_amd/csrc/kvq_inflate.h, the code the GPU's
 inflate kernel runs) through its host entry kvq_inflate_raw_host, and of the BGZF block index
 kvq_bgzf_index: byte-exact against zlib on valid members, the same verdict as zlib under the host
-reader's success rule on corrupted ones.
+reader's success rule on corrupted ones and on the structured corpus of tests/deflate_writer.py
+(distances of the whole window, stored blocks across the ring wrap, zlib's rules at the edges of the
+Huffman headers).  Every call's output slot lies between canary bytes that must stay untouched.
 """
+import ctypes as C
 import gzip
 
 import pytest
 
 import inflate_corpus as IC
-from kvarq_amd import bgzf as B
+from kvarq_amd import _lib, bgzf as B
 from test_host_logic import bgzf
+
+CANARY = 0xC5
+PAD = 64
+
+
+def _inflate_padded(payload, isize):
+    """kvq_inflate_raw_host into an isize-byte slot with PAD canary bytes on both sides -> (status, bytes or None);
+    asserts the canaries are untouched"""
+    payload = bytes(payload)
+    buf = C.create_string_buffer(bytes([CANARY]) * (isize + 2 * PAD), isize + 2 * PAD)
+    st = _lib.lib().kvq_inflate_raw_host(payload, len(payload), C.addressof(buf) + PAD, isize)
+    raw = buf.raw
+    assert raw[:PAD] == bytes([CANARY]) * PAD and raw[PAD + isize:] == bytes([CANARY]) * PAD, 'write outside the slot'
+    return st, (raw[PAD:PAD + isize] if st == B.Z_OK else None)
 
 
 @pytest.mark.parametrize('label,payload,text', IC.valid_corpus(), ids=[c[0] for c in IC.valid_corpus()])
 def test_valid_member_equals_zlib(label, payload, text):
     ok, want = IC.zlib_verdict(payload, len(text))
     assert ok and want == text
-    st, got = B.inflate_raw_host(payload, len(text))
+    st, got = _inflate_padded(payload, len(text))
     assert st == 0, (label, st)
     assert got == text
 
@@ -76,7 +93,7 @@ def test_corrupt_members_fail_exactly_when_zlib_fails():
     n_bad = 0
     for i, (p, isize) in enumerate(corpus):
         ok, want = IC.zlib_verdict(p, isize)
-        st, got = B.inflate_raw_host(p, isize)
+        st, got = _inflate_padded(p, isize)
         assert (st == 0) == ok, (i, st, ok)
         if ok:
             assert got == want, i
@@ -84,6 +101,57 @@ def test_corrupt_members_fail_exactly_when_zlib_fails():
             assert st in (B.Z_DATA_ERROR, B.Z_BUF_ERROR), (i, st)
             n_bad += 1
     assert 1000 < n_bad < len(corpus)                    # the corpus holds both kinds
+
+
+EDGE_VALID = IC.edge_valid()
+EDGE_INVALID = IC.edge_invalid()
+
+
+@pytest.mark.parametrize('name,payload,text,features', EDGE_VALID, ids=[m[0] for m in EDGE_VALID])
+def test_edge_valid_member_equals_zlib(name, payload, text, features):
+    assert IC.zlib_verdict(payload, len(text)) == (True, text)
+    assert _inflate_padded(payload, len(text)) == (B.Z_OK, text)
+    assert B.inflate_raw_host(payload, len(text)) == (B.Z_OK, text)
+
+
+@pytest.mark.parametrize('name,payload,isize,reason', EDGE_INVALID, ids=[m[0] for m in EDGE_INVALID])
+def test_edge_invalid_member_fails_as_zlib_fails(name, payload, isize, reason):
+    assert IC.zlib_verdict(payload, isize)[0] is False
+    st, _ = _inflate_padded(payload, isize)
+    assert st in (B.Z_DATA_ERROR, B.Z_BUF_ERROR), (name, st)
+    if reason not in ('truncated', 'isize'):
+        assert st == B.Z_DATA_ERROR, (name, st)              # the bits are no valid DEFLATE stream, not merely short
+
+
+def test_edge_valid_member_one_byte_short_or_long_of_isize():
+    for name, payload, text, _ in EDGE_VALID:
+        if text:
+            assert _inflate_padded(payload, len(text) - 1)[0] == B.Z_BUF_ERROR, name
+        if len(text) < 65536:
+            assert _inflate_padded(payload, len(text) + 1)[0] == B.Z_BUF_ERROR, name
+
+
+def test_libdeflate_members_equal_zlib():
+    corpus = IC.libdeflate_corpus()
+    if corpus is None:
+        pytest.skip('libdeflate does not load on this machine')
+    for label, payload, text in corpus:
+        assert IC.zlib_verdict(payload, len(text)) == (True, text), label
+        assert _inflate_padded(payload, len(text)) == (B.Z_OK, text), label
+
+
+def test_writer_made_bgzf_members_equal_zlib():
+    import cases
+    t = cases.ragged(11, 500, cases.RAGGED_TARGETS, maxlen=500)
+    z, far = IC.writer_bgzf(t)
+    assert far == 32768
+    off, cs, isz = B.index(z)
+    got = []
+    for o, c, i in zip(off, cs, isz):
+        st, b = _inflate_padded(B.payload(z, o, c), int(i))
+        assert st == 0
+        got.append(b)
+    assert b''.join(got) == gzip.decompress(z) == t
 
 
 def _files():
