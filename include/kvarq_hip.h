@@ -191,7 +191,8 @@ int32_t kvq_scan_reset(kvq_scan *s);
  * record split failed validation, one read flooded a wave's queues) and the batch rescanned,
  * bit 3 = tiles of the seed-filter pass left their records alone (a record longer than a tile's
  * look-ahead, more newlines than its tables hold) and those records were scanned again, bit 4 = the text was inflated
- * on the device (kvq_findseqs_ex, KVQ_FIND_DEVICE_INFLATE) */
+ * on the device (kvq_findseqs_ex, KVQ_FIND_DEVICE_INFLATE or KVQ_FIND_DEVICE_GZIP), bit 5 = a file of it took the speculative
+ * route of KVQ_FIND_DEVICE_GZIP */
 int32_t kvq_scan_path(const kvq_scan *s);
 /* 0 = let the table decide, 1 = force the exhaustive kernel for every sequence */
 void    kvq_scan_force_exhaustive(kvq_scan *s, int32_t on);
@@ -276,6 +277,12 @@ kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
  * inflating compressed data : status=<zlib status> fpos=<stream offset of that BLOCK's first inflated byte>".
  * kvq_scan_path bit 4 tells that the text was inflated on the device. */
 #define KVQ_FIND_DEVICE_INFLATE 1u
+/* KVQ_FIND_DEVICE_GZIP: when EVERY file is a ".gz", each is inflated on the GPU: a BGZF file as above, any other gzip by
+ * speculative chunk decoding (kvq_inflate_gzip_device); otherwise the call is kvq_findseqs.  Results,
+ * stats() after the call and messages are kvq_findseqs's, but for the fpos of "error while inflating compressed data":
+ * for a plain gzip file the stream offset at which the failing DEFLATE block's output starts.  kvq_scan_path bit 5 tells
+ * that a file took the speculative route; kvq_gzip_last_report what it did. */
+#define KVQ_FIND_DEVICE_GZIP 2u
 kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
                           const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags);
 
@@ -371,6 +378,48 @@ int32_t kvq_inflate_bgzf_device(const void *d_in, int64_t in_bytes, const kvq_bg
  * returns nchunks, or -1 when a chunk holds no record start (kvq_last_error: the host route's message, offsets
  * relative to d_data) or on a device failure */
 int64_t kvq_chunk_offsets_device(const void *d_data, int64_t nbytes, int64_t *offsets, int64_t cap);
+
+/* ---- plain gzip by speculative chunk decoding ----------------------------------------------------
+ * A whole gzip file's bytes are cut into chunks of chunk_bytes (>= 64) compressed bytes; each chunk is decoded from the first
+ * dynamic-Huffman block header behind its start with its 32 KiB window unknown, the chain of chunks is checked (a chunk whose
+ * predecessor did not end exactly at its start is decoded again from where it did end), the windows are resolved in order and
+ * the markers replaced.  The text is the host reader's (GzSerial, kvq_findseqs.hip): members crossed by its rules, a file cut
+ * short ends the text, no CRC32 check.  Returns the text's length -- written to out only when it fits out_cap --, or -1 when
+ * the DEFLATE data fail (*status: zlib's status, -3; *err_fpos: the text offset at which the failing block's output starts;
+ * kvq_last_error: the host route's message), -2 on other errors (no gzip header at byte 0: the host route's message). */
+typedef struct kvq_gzip_report {
+    int64_t runs;               /* runs of compressed bytes (one per call here; kvq_findseqs_ex: per batch) */
+    int64_t chunks;             /* chunks the runs were cut into (after merging those without a candidate) */
+    int64_t candidates_tested;  /* bit offsets the block finder examined, up to and including each chunk's candidate */
+    int64_t refuted;            /* chunks whose start the chain check moved (a false candidate, or one behind a false one) */
+    int64_t redecodes;          /* chunk decodes after the first one of each chunk */
+    int64_t slot_overflows;     /* decodes that ran out of slot and were repeated in a larger one */
+    int64_t marker_symbols;     /* text bytes that were decoded as markers of an unknown window and replaced */
+    int64_t input_retries;      /* runs whose last chunk read past the margin behind them (a block or member header longer than
+                                   it) and that were done again with a margin 4x larger; such a run counts once in runs, chunks,
+                                   candidates_tested, refuted, slot_overflows and marker_symbols, as its last attempt does, and
+                                   the decodes of the attempts before it count in redecodes */
+    double  ms_find, ms_decode, ms_resolve, ms_replace;     /* wall time of the phases, every attempt included (each phase ends
+                                                               in a wait for its kernels) */
+} kvq_gzip_report;
+
+/* on the CPU: the same decoder source and chunked algorithm as on the GPU */
+int64_t kvq_inflate_gzip_host(const uint8_t *file, int64_t n, int64_t chunk_bytes, uint8_t *out, int64_t out_cap,
+                              int32_t *status, int64_t *err_fpos, kvq_gzip_report *rep);
+/* on the GPU: d_file and d_out in device memory; writes d_out[0, text length) only, and only when it fits out_cap.  Blocking */
+int64_t kvq_inflate_gzip_device(const void *d_file, int64_t n, int64_t chunk_bytes, void *d_out, int64_t out_cap,
+                                int32_t *status, int64_t *err_fpos, kvq_gzip_report *rep);
+/* the report of the last kvq_inflate_gzip_* or kvq_findseqs_ex call that took the speculative route */
+void    kvq_gzip_last_report(kvq_gzip_report *rep);
+/* test hook, for the last kvq_inflate_gzip_* call: the block finder's candidate per nominal chunk start (-1: none; *ncand of
+ * them, up to ncand_cap written) and per chunk that held its start bit, the bit it ended at (-1: the text ended in it) and its
+ * symbols (up to cap written); returns the number of chunks that held */
+/* test hook: from now on every chunk slot of the speculative route (host and device alike) lies between pad_symbols (0..65536;
+ * 0: none) canary symbols on each side, checked after each decode; returns how many canary symbols were found overwritten since
+ * the call before, and starts counting again */
+int64_t kvq_gzip_slot_canaries(int32_t pad_symbols);
+int64_t kvq_gzip_last_chunks(int64_t *cand, int64_t ncand_cap, int64_t *start_bit, int64_t *end_bit, int64_t *nsym, int64_t cap,
+                             int64_t *ncand);
 
 const char *kvq_version(void);
 

@@ -24,6 +24,15 @@ class LiveStats(C.Structure):
                 ('sigints', C.c_int32), ('stop_requested', C.c_int32)]
 
 
+class GzipReport(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ('runs', 'chunks', 'candidates_tested', 'refuted', 'redecodes',
+                                         'slot_overflows', 'marker_symbols', 'input_retries')] + \
+        [(n, C.c_double) for n in ('ms_find', 'ms_decode', 'ms_resolve', 'ms_replace')]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 i32, i64, u64, vp, cp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p, C.c_char_p
 P = C.POINTER
 
@@ -114,6 +123,11 @@ PROTOTYPES = {
     'kvq_bgzf_index': (i64, [vp, i64, P(i64), P(C.c_uint32), P(C.c_uint32), i64]),
     'kvq_chunk_offsets_device': (i64, [vp, i64, P(i64), i64]),
     'kvq_inflate_bgzf_device': (i32, [vp, i64, vp, i64, vp, i64, vp]),
+    'kvq_inflate_gzip_host': (i64, [vp, i64, i64, vp, i64, P(i32), P(i64), P(GzipReport)]),
+    'kvq_inflate_gzip_device': (i64, [vp, i64, i64, vp, i64, P(i32), P(i64), P(GzipReport)]),
+    'kvq_gzip_last_report': (None, [P(GzipReport)]),
+    'kvq_gzip_slot_canaries': (i64, [i32]),
+    'kvq_gzip_last_chunks': (i64, [P(i64), i64, P(i64), P(i64), P(i64), i64, P(i64)]),
     'kvq_version': (cp, []),
 }
 

@@ -810,6 +810,51 @@ static int64_t device_batch_bytes()
     return (int64_t)(v >= 2 && v <= 1024 ? v : 256) << 20;
 }
 
+// One run of whole BGZF blocks [b0, b1) of a file, its compressed bytes [bl[b0].off, end of bl[b1 - 1]) in g_dev.pin[slot]:
+// the block table (the text goes behind the `carry` bytes of the unfinished chunk, copied from carry_at to the front of
+// text unless it lies there), the copies and kvq_inflate_bgzf enqueued on st, the statuses on their way to g_dev.pstat[slot].
+// *have: the text bytes there will be.  bgzf_run_check reads the statuses once st has been synchronised.
+static int bgzf_run_enqueue(const std::vector<kvq_bgzf_entry_> &bl, size_t b0, size_t b1, int slot, uint8_t *text, int64_t text_cap,
+                            int64_t carry, const uint8_t *carry_at, hipStream_t st, int64_t *have)
+{
+    int rc;
+    const int64_t nb = (int64_t)(b1 - b0), c0 = bl[b0].off, c1 = bl[b1 - 1].off + bl[b1 - 1].size;
+    if ((rc = pinned_grow(&g_dev.ptab[slot], &g_dev.ptab_cap[slot], (size_t)nb * sizeof(kvq_bgzf_block)))) return rc;
+    if ((rc = pinned_grow(&g_dev.pstat[slot], &g_dev.pstat_cap[slot], (size_t)nb * 4))) return rc;
+    kvq_bgzf_block *tab = (kvq_bgzf_block *)g_dev.ptab[slot];
+    int64_t o = carry;
+    for (int64_t i = 0; i < nb; i++) {
+        const kvq_bgzf_entry_ &b = bl[b0 + i];
+        tab[i].in_off = b.off - c0 + b.hdr; tab[i].in_len = b.size - b.hdr - 8; tab[i].isize = b.isize; tab[i].out_off = o;
+        o += b.isize;
+    }
+    *have = o;
+    if ((rc = g_dev.d_comp[slot].ensure((size_t)(c1 - c0)))) return rc;
+    if ((rc = g_dev.d_tab[slot].ensure((size_t)nb * sizeof(kvq_bgzf_block)))) return rc;
+    if ((rc = g_dev.d_stat[slot].ensure((size_t)nb * 4))) return rc;
+    KVQ_HIP(hipMemcpyAsync(g_dev.d_comp[slot].p, g_dev.pin[slot], (size_t)(c1 - c0), hipMemcpyHostToDevice, st));
+    KVQ_HIP(hipMemcpyAsync(g_dev.d_tab[slot].p, tab, (size_t)nb * sizeof(kvq_bgzf_block), hipMemcpyHostToDevice, st));
+    if (carry && carry_at != text) KVQ_HIP(hipMemcpyAsync(text, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, st));
+    if ((rc = kvq_inflate_bgzf_launch(g_dev.d_comp[slot].as<uint8_t>(), c1 - c0, g_dev.d_tab[slot].as<kvq_bgzf_block>(), nb,
+                                      text, text_cap, g_dev.d_stat[slot].as<int32_t>(), st))) return rc;
+    KVQ_HIP(hipMemcpyAsync(g_dev.pstat[slot], g_dev.d_stat[slot].p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    return KVQ_OK;
+}
+
+// the statuses of the run bgzf_run_enqueue enqueued in `slot` (nb blocks; text_fpos: the stream offset of the text's front):
+// the first block that did not inflate, as the route's IOError naming that block's first byte
+static int bgzf_run_check(int slot, int64_t nb, int64_t text_fpos)
+{
+    const int32_t *stat = (const int32_t *)g_dev.pstat[slot];
+    const kvq_bgzf_block *tab = (const kvq_bgzf_block *)g_dev.ptab[slot];
+    for (int64_t i = 0; i < nb; i++)
+        if (stat[i] != 0) {
+            kvq_set_error(KVQ_ERR_IO, "error while inflating compressed data : status=%d fpos=%ld", stat[i], (long)(text_fpos + tab[i].out_off));
+            return KVQ_ERR_IO;
+        }
+    return KVQ_OK;
+}
+
 // The walk of stream_batches for files that are BGZF to the end, with the inflate and the cuts on the GPU.  Per batch: a run of
 // whole blocks is read into pinned memory (the next run is read while the GPU inflates this one), copied to the device and
 // inflated behind the unfinished chunk the batch before left (copied device to device to the front of the text buffer, so that
@@ -862,29 +907,11 @@ static int stream_device(Sink &sink, kvq_scan *s, const std::vector<BgzfFile> &f
     if ((rc = read_run(cur, 0))) return rc;
     for (int k = 0; cur.valid && !g_stop.load(); k++) {
         const int slot = k & 1;
-        const auto &bl = files[cur.f].blocks;
         const int64_t nb = (int64_t)(cur.b1 - cur.b0);
-        if ((rc = pinned_grow(&g_dev.ptab[slot], &g_dev.ptab_cap[slot], (size_t)nb * sizeof(kvq_bgzf_block)))) return rc;
-        if ((rc = pinned_grow(&g_dev.pstat[slot], &g_dev.pstat_cap[slot], (size_t)nb * 4))) return rc;
-        kvq_bgzf_block *tab = (kvq_bgzf_block *)g_dev.ptab[slot];
-        int64_t o = carry;
-        for (int64_t i = 0; i < nb; i++) {
-            const kvq_bgzf_entry_ &b = bl[cur.b0 + i];
-            tab[i].in_off = b.off - cur.c0 + b.hdr; tab[i].in_len = b.size - b.hdr - 8; tab[i].isize = b.isize; tab[i].out_off = o;
-            o += b.isize;
-        }
-        const int64_t have = o;
-        if ((rc = g_dev.d_comp[slot].ensure((size_t)(cur.c1 - cur.c0)))) return rc;
-        if ((rc = g_dev.d_tab[slot].ensure((size_t)nb * sizeof(kvq_bgzf_block)))) return rc;
-        if ((rc = g_dev.d_stat[slot].ensure((size_t)nb * 4))) return rc;
         uint8_t *text = g_dev.d_text[tb].as<uint8_t>();
-        KVQ_HIP(hipMemcpyAsync(g_dev.d_comp[slot].p, g_dev.pin[slot], (size_t)(cur.c1 - cur.c0), hipMemcpyHostToDevice, st));
-        KVQ_HIP(hipMemcpyAsync(g_dev.d_tab[slot].p, tab, (size_t)nb * sizeof(kvq_bgzf_block), hipMemcpyHostToDevice, st));
         const uint8_t *carry_at = g_dev.d_text[cb].as<uint8_t>() + carry_src;
-        if (carry && carry_at != text) KVQ_HIP(hipMemcpyAsync(text, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, st));
-        if ((rc = kvq_inflate_bgzf_launch(g_dev.d_comp[slot].as<uint8_t>(), cur.c1 - cur.c0, g_dev.d_tab[slot].as<kvq_bgzf_block>(), nb,
-                                          text, text_cap, g_dev.d_stat[slot].as<int32_t>(), st))) return rc;
-        KVQ_HIP(hipMemcpyAsync(g_dev.pstat[slot], g_dev.d_stat[slot].p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        int64_t have = 0;
+        if ((rc = bgzf_run_enqueue(files[cur.f].blocks, cur.b0, cur.b1, slot, text, text_cap, carry, carry_at, st, &have))) return rc;
         int64_t *cut = (int64_t *)g_dev.pcut;
         int64_t *d_cut = g_dev.d_cut.as<int64_t>();
         if ((rc = kvq_cut_chunks_launch(text, have, 0, fill, d_cut + 8, KVQ_CUT_CAP, d_cut, st))) return rc;
@@ -895,12 +922,7 @@ static int stream_device(Sink &sink, kvq_scan *s, const std::vector<BgzfFile> &f
         else if (cur.f + 1 < files.size()) nxt = next_run(cur.f + 1, 0);
         if (nxt.valid && (rc = read_run(nxt, slot ^ 1))) return rc;
         KVQ_HIP(hipStreamSynchronize(st));
-        const int32_t *stat = (const int32_t *)g_dev.pstat[slot];
-        for (int64_t i = 0; i < nb; i++)
-            if (stat[i] != 0) {
-                kvq_set_error(KVQ_ERR_IO, "error while inflating compressed data : status=%d fpos=%ld", stat[i], (long)(text_fpos + tab[i].out_off));
-                return KVQ_ERR_IO;
-            }
+        if ((rc = bgzf_run_check(slot, nb, text_fpos))) return rc;
         std::vector<int64_t> off;
         for (;;) {
             if (cut[3]) {
@@ -935,15 +957,207 @@ static int stream_device(Sink &sink, kvq_scan *s, const std::vector<BgzfFile> &f
     return KVQ_OK;
 }
 
+// ---------------------------------------------------------------------------
+// the device route of any gzip (kvq_findseqs_ex with KVQ_FIND_DEVICE_GZIP)
+// ---------------------------------------------------------------------------
+
+struct GzFile { std::string name; int64_t size = 0; bool bgzf = false; std::vector<kvq_bgzf_entry_> blocks; };
+
+// is every file a ".gz"?  Each one's kind: BGZF to its end (its blocks, as bgzf_files walks them) or any other gzip
+static bool gz_files(const char *const *files, int nfiles, std::vector<GzFile> &out)
+{
+    out.clear();
+    for (int i = 0; i < nfiles; i++) {
+        GzFile f; f.name = files[i];
+        if (!(f.name.size() >= 3 && f.name.compare(f.name.size() - 3, 3, ".gz") == 0)) return false;
+        FILE *fd = fopen(f.name.c_str(), "rb");
+        if (!fd) return false;
+        fseek(fd, 0, SEEK_END); f.size = ftell(fd);
+        const int fdn = fileno(fd);
+        auto read = [&](uint8_t *dst, int64_t k, int64_t at) -> int64_t { const ssize_t got = pread(fdn, dst, (size_t)k, (off_t)at); return got < 0 ? 0 : (int64_t)got; };
+        f.bgzf = kvq_bgzf_walk(read, f.size, f.blocks);
+        fclose(fd);
+        out.push_back(std::move(f));
+    }
+    return nfiles > 0;
+}
+
+static struct GzRoute { DevBuf d_comp, d_win; void *pin = nullptr; size_t pin_cap = 0; } g_gz;
+
+// compressed bytes per run of a plain gzip file (a quarter of the text a batch holds) and per chunk (KVQ_GZIP_CHUNK_KB)
+static int64_t gz_chunk_bytes()
+{
+    const char *e = getenv("KVQ_GZIP_CHUNK_KB");
+    const long v = e ? atol(e) : 0;
+    return (int64_t)(v >= 1 && v <= 65536 ? v : 128) << 10;
+}
+
+// The walk of stream_device for files that are all gzip: a BGZF file by runs of whole blocks (the block route's kernel), any
+// other by runs of compressed bytes through the chunked algorithm of kernels_gzip.hip, each run starting at the block boundary
+// (and with the window, kept on the device) where the run before it ended; the last chunk of a run reads on into a margin of
+// the bytes behind it.  From the text on, both go the block route's way: the unfinished chunk to the front, kvq_cut_chunks,
+// kvq_scan_staged.  The host reader's estimate of the total is worked out from where its serial reader would have read to.
+template <class Sink>
+static int stream_gzip_device(Sink &sink, kvq_scan *s, const std::vector<GzFile> &files, int64_t *parsed, int64_t *total_out)
+{
+    int rc;
+    int64_t size_all = 0;
+    for (auto &f : files) size_all += f.size;
+    sink.begin(size_all);
+    const int64_t batch_cap = device_batch_bytes(), text_cap0 = batch_cap + KVQ_SCANBUFSIZE + 64;
+    for (int i = 0; i < 2; i++) if ((rc = g_dev.d_text[i].ensure((size_t)text_cap0))) return rc;
+    if ((rc = g_dev.d_cut.ensure((8 + KVQ_CUT_CAP) * 8))) return rc;
+    if ((rc = pinned_grow(&g_dev.pcut, &g_dev.pcut_cap, (8 + KVQ_CUT_CAP) * 8))) return rc;
+    if ((rc = g_gz.d_win.ensure(KVQ_INF_WINDOW))) return rc;
+    kvq_config cfg; kvq_config_get(&cfg);
+    hipStream_t st = s->stream;
+    g_gz_report = kvq_gzip_report();
+    const int64_t chunk_bytes = gz_chunk_bytes(), run_bytes = std::max<int64_t>(batch_cap / 4, 64 << 10);
+
+    int64_t fpos = 0, ftell0 = 0, total = size_all;
+    int tb = 0;
+    for (size_t fi = 0; fi < files.size() && !g_stop.load(); fi++) {
+        const GzFile &F = files[fi];
+        FILE *fd = fopen(F.name.c_str(), "rb");
+        if (!fd) { kvq_set_error(KVQ_ERR_IO, "cannot open file"); return KVQ_ERR_IO; }
+        struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{ fd };
+        const int fdn = fileno(fd);
+        auto read_into_pin = [&](int64_t at, int64_t n) -> int {
+            int rc2 = pinned_grow(&g_gz.pin, &g_gz.pin_cap, (size_t)std::max<int64_t>(n, 1));
+            if (rc2) return rc2;
+            if (n > 0 && !pread_run(fdn, (uint8_t *)g_gz.pin, n, at, cfg.nthreads)) {
+                kvq_set_error(KVQ_ERR_IO, "could not read enough bytes from .fastq.gz : I/O error"); return KVQ_ERR_IO;
+            }
+            return KVQ_OK;
+        };
+        int64_t carry = 0, carry_src = 0, fill = 0, text_fpos = fpos, consumed = 0;
+        int cb = tb;
+        // plain gzip: where the next run starts, the window's valid bytes, where the serial reader's reads of the member started
+        int64_t gz_bit = 0, gz_h = 0; int32_t gz_wl = 0;
+        size_t b0 = 0;                                                 // BGZF: the next block
+        if (!F.bgzf) {
+            const int64_t k = std::min<int64_t>(F.size, 1 << 20);
+            if ((rc = read_into_pin(0, k))) return rc;
+            gz_bit = gz_first_member((const uint8_t *)g_gz.pin, k, F.size);
+            if (gz_bit < 0) return KVQ_ERR_IO;
+            gz_h = gz_bit >> 3;
+            s->path_bits |= 32;
+        }
+        bool eof = false;
+        while (!eof && !g_stop.load()) {
+            uint8_t *text = g_dev.d_text[tb].as<uint8_t>();
+            const uint8_t *carry_at = g_dev.d_text[cb].as<uint8_t>() + carry_src;
+            if (carry && carry_at != text) KVQ_HIP(hipMemcpyAsync(text, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, st));
+            int64_t have = carry, isz = 0;
+            if (F.bgzf) {
+                // a run of whole blocks, inflated by kvq_inflate_bgzf as stream_device does
+                const auto &bl = F.blocks;
+                size_t b1 = b0;
+                while (b1 < bl.size() && (b1 == b0 || isz + bl[b1].isize <= batch_cap)) isz += bl[b1++].isize;
+                const int64_t c0 = bl[b0].off, c1 = bl[b1 - 1].off + bl[b1 - 1].size;
+                if ((rc = pinned_grow(&g_dev.pin[0], &g_dev.pin_cap[0], (size_t)(c1 - c0)))) return rc;
+                if (!pread_run(fdn, (uint8_t *)g_dev.pin[0], c1 - c0, c0, cfg.nthreads)) {
+                    kvq_set_error(KVQ_ERR_IO, "could not read enough bytes from .fastq.gz : I/O error"); return KVQ_ERR_IO;
+                }
+                // (the carry is in front of text already)
+                if ((rc = bgzf_run_enqueue(bl, b0, b1, 0, text, (int64_t)g_dev.d_text[tb].cap, carry, text, st, &have))) return rc;
+                KVQ_HIP(hipStreamSynchronize(st));
+                if ((rc = bgzf_run_check(0, (int64_t)(b1 - b0), text_fpos))) return rc;
+                b0 = b1; eof = b1 == bl.size();
+                consumed = eof ? F.size : c1;
+            } else {
+                // a run of compressed bytes [rb, re) and a margin behind it
+                const int64_t rb = gz_bit >> 3, re = std::min<int64_t>(F.size, rb + run_bytes);
+                GzRunOut ro;
+                for (int64_t margin = 1 << 20; ; margin *= 4) {
+                    const int64_t n = std::min<int64_t>(F.size, re + margin) - rb;
+                    if ((rc = read_into_pin(rb, n))) return rc;
+                    if ((rc = g_gz.d_comp.ensure((size_t)std::max<int64_t>(n, 1)))) return rc;
+                    KVQ_HIP(hipMemcpyAsync(g_gz.d_comp.p, g_gz.pin, (size_t)n, hipMemcpyHostToDevice, st));
+                    GzDeviceBackend be; be.d_in = g_gz.d_comp.as<uint8_t>(); be.n = n; be.file_end = F.size - rb; be.st = st;
+                    be.d_win0 = g_gz.d_win.as<uint8_t>(); be.d_win_last = g_gz.d_win.as<uint8_t>();
+                    be.d_text = text + carry; be.text_cap = (int64_t)g_dev.d_text[tb].cap - carry;
+                    be.grow = [&](int64_t need) -> int {
+                        // the text buffer grows; the carry at its front moves along
+                        DevBuf nb;
+                        int rc2 = nb.ensure((size_t)(carry + need + need / 4 + KVQ_SCANBUFSIZE + 64));
+                        if (rc2) return rc2;
+                        if (carry) KVQ_HIP(hipMemcpyAsync(nb.p, text, (size_t)carry, hipMemcpyDeviceToDevice, st));
+                        KVQ_HIP(hipStreamSynchronize(st));
+                        g_dev.d_text[tb].release(); g_dev.d_text[tb] = nb;
+                        text = nb.as<uint8_t>(); be.d_text = text + carry; be.text_cap = (int64_t)nb.cap - carry;
+                        if (cb == tb) carry_src = 0;
+                        return KVQ_OK;
+                    };
+                    const int64_t stop = re >= F.size ? INT64_MAX : (re - rb) * 8;
+                    kvq_gzip_report part = kvq_gzip_report();
+                    if ((rc = gz_run(be, n, F.size - rb, gz_bit - rb * 8, stop, gz_wl, chunk_bytes, part, ro, false))) return rc;
+                    const bool again = ro.status == KVQ_INF_NEED_INPUT && rb + n < F.size;
+                    gz_report_add(g_gz_report, part, again);
+                    if (!again) break;
+                }
+                if (ro.status) {
+                    kvq_set_error(KVQ_ERR_IO, "error while inflating compressed data : status=%d fpos=%ld", ro.status == KVQ_INF_NEED_INPUT ? KVQ_INF_BUF_ERROR : ro.status,
+                                  (long)(text_fpos + carry + ro.err_o));
+                    return KVQ_ERR_IO;
+                }
+                isz = ro.text; have += ro.text;
+                if (ro.mbyte >= 0) gz_h = rb + ro.mbyte;
+                eof = ro.ended;
+                if (!eof) { gz_bit = rb * 8 + ro.next_bit; gz_wl = (int32_t)ro.wl; consumed = std::min<int64_t>(F.size, gz_bit >> 3); }
+                else if (ro.end_how == 1) {
+                    // GzSerial reads a member's data a KVQ_SCANBUFSIZE at a time from behind its header, up to the byte behind its final block
+                    const int64_t e = rb + ro.end_byte, reads = (e - gz_h + KVQ_SCANBUFSIZE - 1) / KVQ_SCANBUFSIZE;
+                    consumed = std::min<int64_t>(F.size, gz_h + reads * KVQ_SCANBUFSIZE);
+                } else consumed = ro.end_how == 2 ? rb + ro.end_byte : F.size;
+                text = g_dev.d_text[tb].as<uint8_t>();
+            }
+            // the cuts, as stream_device makes them
+            int64_t *cut = (int64_t *)g_dev.pcut;
+            int64_t *d_cut = g_dev.d_cut.as<int64_t>();
+            std::vector<int64_t> off;
+            int64_t cs = 0, cfill = fill;
+            for (;;) {
+                if ((rc = kvq_cut_chunks_launch(text, have, cs, cfill, d_cut + 8, KVQ_CUT_CAP, d_cut, st))) return rc;
+                KVQ_HIP(hipMemcpyAsync(cut, d_cut, (8 + KVQ_CUT_CAP) * 8, hipMemcpyDeviceToHost, st));
+                KVQ_HIP(hipStreamSynchronize(st));
+                if (cut[3]) {
+                    kvq_set_error(KVQ_ERR_RUNTIME, "could find beginning of record; read %ld bytes up to %ld", (long)cut[4], (long)(text_fpos + cut[5]));
+                    return KVQ_ERR_RUNTIME;
+                }
+                off.insert(off.end(), cut + 8, cut + 8 + cut[0]);
+                cs = cut[1]; cfill = cut[2];
+                if (cut[0] < KVQ_CUT_CAP) break;
+            }
+            fill = cfill;
+            fpos += isz;
+            if (ftell0 + consumed > 0)
+                total = (int64_t)(size_t)((float)size_all * fpos / (ftell0 + consumed));          // the host reader's estimate (883-884)
+            if (eof) { if (have > cs) off.push_back(cs); cs = have; }
+            const bool handed = !off.empty();
+            if (handed) {
+                off.push_back(cs);
+                if ((rc = sink.batch(text, cs, off.data(), (int64_t)off.size() - 1, text_fpos, fpos, total))) return rc;
+            }
+            if (eof) { ftell0 += consumed; }
+            else { carry = have - cs; carry_src = cs; cb = tb; fill -= cs; text_fpos += cs; }
+            if (handed) tb ^= 1;
+        }
+    }
+    *parsed = fpos; *total_out = total;
+    return KVQ_OK;
+}
+
 // one pass over the files with the current arena; KVQ_NEED_RESCAN asks for another.  bz: the files' BGZF blocks when the
 // device-inflate route was taken
 static int findseqs_pass(kvq_scan *s, const char *const *files, int nfiles, uint8_t *pin, uint8_t *pin2, int64_t pin_cap,
-                         const std::vector<BgzfFile> *bz = nullptr)
+                         const std::vector<BgzfFile> *bz = nullptr, const std::vector<GzFile> *gz = nullptr)
 {
-    ScanSink sink; sink.s = s; sink.staged = bz != nullptr;
+    ScanSink sink; sink.s = s; sink.staged = bz != nullptr || gz != nullptr;
     int64_t parsed = 0, total = 0;
     const double tp0 = now_ms();
     int rc = bz ? stream_device(sink, s, *bz, &parsed, &total)
+           : gz ? stream_gzip_device(sink, s, *gz, &parsed, &total)
                 : stream_batches(sink, files, nfiles, pin, pin_cap, &parsed, &total, pin2);                 // two host buffers
     if (g_timing) fprintf(stderr, "findseqs pass: stream %.1f ms\n", now_ms() - tp0);
     if (rc) return rc;
@@ -1026,8 +1240,11 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
     const int64_t pin_cap = BATCH_BYTES + 2 * KVQ_SCANBUFSIZE;
     // the device-inflate route: asked for, and every file is BGZF to its end (else the call takes the host route unchanged)
     std::vector<BgzfFile> bz;
-    const bool dev = s && (flags & KVQ_FIND_DEVICE_INFLATE) && bgzf_files(files, nfiles, bz);
-    if (s && !dev && !g_pin && hipHostMalloc((void **)&g_pin, (size_t)pin_cap * 2, hipHostMallocDefault) != hipSuccess) {
+    const bool dev = s && (flags & (KVQ_FIND_DEVICE_INFLATE | KVQ_FIND_DEVICE_GZIP)) && bgzf_files(files, nfiles, bz);
+    // ... or any gzip: every file a ".gz", BGZF or not (each one takes its own way)
+    std::vector<GzFile> gzf;
+    const bool dev_any = s && !dev && (flags & KVQ_FIND_DEVICE_GZIP) && gz_files(files, nfiles, gzf);
+    if (s && !dev && !dev_any && !g_pin && hipHostMalloc((void **)&g_pin, (size_t)pin_cap * 2, hipHostMallocDefault) != hipSuccess) {
         kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for scanning"); g_pin = nullptr;
     }
     uint8_t *const pin = g_pin;
@@ -1038,9 +1255,10 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         if (v >= 2 && (v << 20) < BATCH_BYTES) use_cap = ((int64_t)v << 20) + 2 * KVQ_SCANBUFSIZE;
     }
     const double tf2 = now_ms();
-    if (s && (pin || dev)) {
+    if (s && (pin || dev || dev_any)) {
         for (int attempt = 0; attempt < 4; attempt++) {
             const int rc = dev ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, &bz)
+                         : dev_any ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, nullptr, &gzf)
                                : findseqs_pass(s, files, nfiles, pin, pin + pin_cap, use_cap);
             if (rc != KVQ_NEED_RESCAN) break;
             // the hit arena was too small (it has been enlarged): scan again from the start
@@ -1051,7 +1269,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
     const double tf3 = now_ms();
     if (s && s->stream) (void)hipStreamSynchronize(s->stream);        // nothing may still be reading the host buffers
     if (g_timing) fprintf(stderr, "findseqs: table+scan %.1f  pinned alloc %.1f  passes %.1f  free %.1f ms\n", tf1 - tf0, tf2 - tf1, tf3 - tf2, now_ms() - tf3);
-    if (s && dev) s->path_bits |= 16;                                 // (kvq_scan_path bit 4: the text was inflated on the device)
+    if (s && (dev || dev_any)) s->path_bits |= 16;                    // (kvq_scan_path bit 4: the text was inflated on the device; bit 5,
+                                                                      // set by stream_gzip_device: a file took the speculative route)
     g_running = 0;
     if (s) s->t = t;          // the scan owns its table: destroyed with it (kvq_findseqs_free)
     else if (t) kvq_table_destroy(t);

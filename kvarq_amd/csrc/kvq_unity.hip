@@ -8,5 +8,6 @@
 #include "synth.hip"
 #include "kvq_runtime.hip"
 #include "kernels_inflate.hip"
+#include "kernels_gzip.hip"
 #include "kvq_findseqs.hip"
 #include "kvq_dist.hip"

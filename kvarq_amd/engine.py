@@ -106,8 +106,9 @@ def _stats_dict(readlengths, longest, nseqbasehits, nseqhits, parsed, total, sig
 
 
 _last_inflate = None
-INFLATE_FLAGS = {'host': 0, 'device': 1}           # KVQ_FIND_DEVICE_INFLATE
+INFLATE_FLAGS = {'host': 0, 'device': 1, 'device_any': 2}     # KVQ_FIND_DEVICE_INFLATE, KVQ_FIND_DEVICE_GZIP
 PATH_DEVICE_INFLATE = 0x10                         # kvq_scan_path bit 4
+PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
 
 
 def findseqs(fname, sequences, *, inflate='host'):
@@ -120,11 +121,15 @@ def findseqs(fname, sequences, *, inflate='host'):
 
     inflate='device' (not in the reference): when every file is BGZF (bgzip) to its
     end, the compressed blocks go to the GPU and are inflated, cut and scanned there;
-    otherwise the call is the default one.  last_inflate() tells which route ran."""
+    otherwise the call is the default one.  inflate='device_any': when every file is a
+    ``.gz``, each is inflated on the GPU -- a BGZF file by its blocks, any other gzip by
+    speculative chunk decoding --; otherwise the call is the default
+    one.  last_inflate() tells which route ran, last_inflate_report() what the
+    speculative route did."""
     import os, time
     global _last_inflate
     if inflate not in INFLATE_FLAGS:
-        raise ValueError("inflate must be 'host' or 'device'")
+        raise ValueError("inflate must be 'host', 'device' or 'device_any'")
     _last_inflate = None
     t_in = time.perf_counter()
     L = _lib.lib()
@@ -168,7 +173,8 @@ def findseqs(fname, sequences, *, inflate='host'):
     t_1 = time.perf_counter()
     try:
         if h:
-            _last_inflate = 'device' if L.kvq_scan_path(h) & PATH_DEVICE_INFLATE else 'host'
+            path = L.kvq_scan_path(h)
+            _last_inflate = ('device_gzip' if path & PATH_DEVICE_GZIP else 'device' if path & PATH_DEVICE_INFLATE else 'host')
         code, _ = _lib.last_error()
         if not h or code:
             _raise_last()
@@ -208,8 +214,17 @@ def findseqs(fname, sequences, *, inflate='host'):
 
 def last_inflate():
     """where the text of the last findseqs call was inflated: 'device' (the BGZF route on the
-    GPU), 'host' (the reader on the CPU, plain files included), or None before any call"""
+    GPU), 'device_gzip' (inflate='device_any' and a file took the speculative route on the GPU),
+    'host' (the reader on the CPU, plain files included), or None before any call"""
     return _last_inflate
+
+
+def last_inflate_report():
+    """what the speculative gzip route did in the last call that took it (kvq_gzip_report as a dict:
+    runs, chunks, candidates_tested, refuted, redecodes, slot_overflows, marker_symbols)"""
+    rep = _lib.GzipReport()
+    _lib.lib().kvq_gzip_last_report(C.byref(rep))
+    return rep.as_dict()
 
 
 def _sigints():

@@ -285,3 +285,12 @@ def inflate_bgzf_device(d_in, in_bytes, d_blocks, nblocks, d_out, out_bytes, d_s
     addresses as ints (e.g. torch tensors' data_ptr()).  Blocks until done."""
     _check(_lib.lib().kvq_inflate_bgzf_device(C.c_void_p(d_in), in_bytes, C.c_void_p(d_blocks), nblocks,
                                                C.c_void_p(d_out), out_bytes, C.c_void_p(d_status)))
+
+
+def inflate_gzip_device(d_file, n, chunk_bytes, d_out, out_cap):
+    """kvq_inflate_gzip_device: a whole gzip file's bytes in device memory (d_file, n bytes) inflated
+    by speculative chunk decoding into d_out (out_cap bytes; written only when the text fits).
+    Returns (text length, report dict); kvarq_amd.gzip_spec.GzipError when the DEFLATE data fail,
+    IOError for a missing gzip header.  Blocks until done."""
+    from . import gzip_spec
+    return gzip_spec._call(_lib.lib().kvq_inflate_gzip_device, C.c_void_p(d_file), n, chunk_bytes, out_cap, C.c_void_p(d_out))
