@@ -176,6 +176,23 @@ void          *kvq_scan_device_counters_own(const kvq_scan *s);   /* ... this ra
 int64_t        kvq_scan_parsed(const kvq_scan *s);            /* fastq_parsed          */
 int64_t        kvq_scan_total(const kvq_scan *s);             /* fastq_size_estimated  */
 
+/* ---- the records of the hits (the reference's Analyser.extract_hits, kvarq/analyse.py:536-540) ----
+ * A hit's RECORD is the bytes of the FastQ record whose bases line holds the hit's file_pos (file_pos is the first base of
+ * the trimmed read, so all hits of one read share it): from the first byte of its identifier line to the end of its quality
+ * line, that line's '\n' included; when the stream ends without a final newline, to the end of the stream.  The bytes are
+ * raw (a '\r' stays).  They are gathered on the GPU while the batch's text is in device memory, each read's record stored
+ * once, whatever number of hits it has.
+ * kvq_scan_set_records: on or off, before the first batch or after kvq_scan_reset (KVQ_ERR_RUNTIME otherwise), and not with
+ * a communicator (records are not gathered across ranks: KVQ_ERR_RUNTIME, from this call or from kvq_scan_set_comm).  A
+ * store too small for the records of a scan works like an overflowing hit arena: grown, and KVQ_ERR_RESCAN for host batches.
+ * After kvq_scan_finish: hit i's record is blob[off[i], off[i] + len[i]), hits in canonical order; kvq_scan_record_bytes:
+ * bytes of the distinct records held.  NULL / 0 when records are off. */
+int32_t        kvq_scan_set_records(kvq_scan *s, int32_t on);
+const uint8_t *kvq_scan_record_blob(const kvq_scan *s);
+const int64_t *kvq_scan_hit_record_off(const kvq_scan *s);
+const int32_t *kvq_scan_hit_record_len(const kvq_scan *s);
+int64_t        kvq_scan_record_bytes(const kvq_scan *s);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -283,6 +300,9 @@ kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
  * for a plain gzip file the stream offset at which the failing DEFLATE block's output starts.  kvq_scan_path bit 5 tells
  * that a file took the speculative route; kvq_gzip_last_report what it did. */
 #define KVQ_FIND_DEVICE_GZIP 2u
+/* KVQ_FIND_RECORDS: the scan keeps the record of every hit (kvq_scan_set_records; the accessors below).  It ORs with the two
+ * inflate flags; alone it is the host route with records. */
+#define KVQ_FIND_RECORDS 4u
 kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
                           const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags);
 

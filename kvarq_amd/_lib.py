@@ -11,6 +11,7 @@ MAX_READLENGTH = 1024
 OK, ERR_FORMAT, ERR_IO, ERR_MEMORY, ERR_RUNTIME, ERR_TYPE, ERR_DEVICE, ERR_RESCAN = range(8)
 CTR_RECORDS, CTR_LONGEST, CTR_HITS, CTR_READLENGTHS = 0, 1, 2, 4
 CELL_DENSE, CELL_DIAG, CELL_STAMPS = 0x1000, 0x2000, 0x4000      # kvq_scan_kernel_pick / kvq_scan_kernel
+FIND_RECORDS = 4                                                 # kvq_findseqs_ex: keep the records of the hits
 
 
 class Config(C.Structure):
@@ -76,6 +77,11 @@ PROTOTYPES = {
     'kvq_scan_device_counters_own': (vp, [vp]),
     'kvq_scan_parsed': (i64, [vp]),
     'kvq_scan_total': (i64, [vp]),
+    'kvq_scan_set_records': (i32, [vp, i32]),
+    'kvq_scan_record_blob': (vp, [vp]),
+    'kvq_scan_hit_record_off': (P(i64), [vp]),
+    'kvq_scan_hit_record_len': (P(i32), [vp]),
+    'kvq_scan_record_bytes': (i64, [vp]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_gap_ms': (C.c_double, [vp, vp]),

@@ -44,6 +44,7 @@ class Analyser(object):
         self.fastq = None
         self.coverages = None                   # OrderedDict name -> Coverage
         self.hits = self.hitseqs = self.stats = self.config = None
+        self.records = None                     # the FastQ record of every hit, when ``scan`` kept them (records=True)
         self.results = {}                       # testsuite interpretation is out of scope: stays empty
         self.scantime = -1
 
@@ -62,9 +63,11 @@ class Analyser(object):
 
     # -- scanning ------------------------------------------------------------------
 
-    def scan(self, fastq, templates, do_reverse=True):
+    def scan(self, fastq, templates, do_reverse=True, records=False):
         """``fastq``: a :class:`kvarq_amd.fastq.Fastq`; ``templates``: ordered mapping name -> plus-strand
-        template (``Sequence``, text, or ``(text, left, right)``).  May raise ``FastqFileFormatException``."""
+        template (``Sequence``, text, or ``(text, left, right)``).  May raise ``FastqFileFormatException``.
+        ``records=True`` keeps the FastQ record of every hit, gathered on the GPU during the scan, for
+        :meth:`extract_hits`."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
         self.fastq_sizes = fastq.filesizes()
@@ -76,9 +79,10 @@ class Analyser(object):
         if do_reverse:
             seqs += [c.minus_seq.bases for c in self.coverages.values()]
         t0 = time.time()
-        ret = engine.findseqs(self.fastq_filenames, seqs)
+        ret = engine.findseqs(self.fastq_filenames, seqs, records=records)
         lo.debug('found %d hits' % len(ret['hits']))
         self.stats, self.hits, self.hitseqs = ret['stats'], ret['hits'], ret['hitseqs']
+        self.records = ret.get('records')
         self.scantime = time.time() - t0
         self.update_coverages()
 
@@ -92,6 +96,25 @@ class Analyser(object):
             if isinstance(hitseq, bytes):
                 hitseq = hitseq.decode('latin-1')
             self.coverage_at(hit.seq_nr).apply_hit(hit, hitseq, hit.seq_nr < n)
+
+    # -- the reads behind the hits (analyse.py:536-540) ------------------------------
+
+    def extract_hits(self, fname):
+        """writes the FastQ record of every hit to ``fname``, one entry per hit in ``.hits`` order (duplicates
+        included): the record's four lines, each stripped of surrounding whitespace, joined by newlines, plus a
+        newline -- what the reference's ``Fastq.readrecordat`` returns.  The records ``scan(records=True)`` kept
+        are used; without them (an analyser rebuilt by ``decode``, a scan without records) each record is read
+        from the file with ``Fastq.readrecordat``, the reference's way."""
+        assert self.hits is not None, 'no hits to extract'
+        t0 = time.time()
+        with open(fname, 'wb') as out:
+            if self.records is not None:
+                for rec in self.records:
+                    out.write(format_record(rec))
+            else:
+                for hit in self.hits:
+                    out.write(self.fastq.readrecordat(hit).encode('latin-1'))
+        lo.debug('extract_hits: %d records in %.3f s' % (len(self.hits), time.time() - t0))
 
     # -- the .json object ---------------------------------------------------------
 
@@ -151,6 +174,16 @@ class Analyser(object):
             if len(c.coverage) != len(c.plus_seq):
                 raise DecodingException('coverage of "%s" does not fit its template' % name)
             self.coverages[str(name)] = c
+
+
+def format_record(record):
+    """a hit's raw record (bytes or latin-1 ``str``) as ``extract_hits`` writes it: its four lines, each ``strip()``ped
+    of ASCII whitespace, joined by ``b'\\n'``, plus ``b'\\n'`` (a record cut short by the end of the text has empty lines
+    after its last one, as ``readline`` gives at the end of a file)"""
+    if isinstance(record, str):
+        record = record.encode('latin-1')
+    lines = (record.split(b'\n') + [b''] * 4)[:4]
+    return b'\n'.join(line.strip() for line in lines) + b'\n'
 
 
 def json_dump(data, fd, indent=2, max_indent_level=2):

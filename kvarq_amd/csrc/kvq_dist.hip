@@ -234,6 +234,10 @@ int kvq_comm_max_status(kvq_comm *c, unsigned long long mine, unsigned long long
 extern "C" int32_t kvq_scan_set_comm(kvq_scan *s, kvq_comm *c)
 {
     kvq_clear_error();
+    if (c && s->records_on) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "records are not gathered across ranks: a scan that keeps records cannot take a communicator");
+        return KVQ_ERR_RUNTIME;
+    }
     if (c) {
         int rc;
         if ((rc = s->d_finish.ensure(sizeof(KvqFinishState) + 256))) return rc;

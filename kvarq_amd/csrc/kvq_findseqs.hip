@@ -1233,6 +1233,7 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         t = kvq_table_create(seqs, seqlens, nseq, nullptr);
         s = t ? kvq_scan_create(t, nullptr) : nullptr;
     }
+    if (s && kvq_scan_set_records(s, (flags & KVQ_FIND_RECORDS) ? 1 : 0)) { kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr; }
     const double tf1 = now_ms();
     // the two pinned host buffers outlive the call: pinning and unpinning 130 MB costs more than
     // streaming a 1 GB file through them (only one findseqs runs at a time, g_running)

@@ -167,6 +167,17 @@ struct kvq_scan {
     DevBuf d_ctr_all;                             // the counters of all ranks, summed (the rank's own stay in d_ctr: a repeated finish sums them afresh)
     DevBuf d_gather_cnt, d_gather_res;            // kvq_scan_gather_hits: counts of the ranks, the gathered arrays
     bool reduced = false, gathered = false;
+    // the records of the hits (kvq_scan_set_records, kernels_records.hip): a table keyed by file_pos, a store of record
+    // bytes, and the per-hit (offset, length) the finish looks up; all of it lands in pin_rec
+    bool records_on = false;
+    DevBuf d_rkey, d_roff, d_rlen, d_rdir, d_rstore, d_rsmall, d_rres;
+    uint32_t rslots = 0;                          // slots of the table (a power of two, >= 2 x arena_cap)
+    unsigned long long rstore_cap = 0;            // bytes of the store (KVQ_RECORD_CAP caps the first one)
+    uint8_t *pin_rec = nullptr; size_t pin_rec_cap = 0;   // pinned: the record words, offsets [rec_hcap], lengths [rec_hcap], store bytes [rec_scap]
+    uint64_t rec_hcap = 0, rec_scap = 0;
+    uint64_t rec_tail_n = 0, rec_tail_b = 0;      // what the tail fetched ahead of time (offsets / lengths of that many hits, that many store bytes)
+    uint64_t rec_spec_n = 4096, rec_spec_b = 1u << 20;   // ... guessed from the last scan of this handle
+    int64_t rec_store_bytes = 0;                  // store bytes of the finished scan
 };
 
 // kernels_seeded.hip

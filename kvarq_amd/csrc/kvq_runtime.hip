@@ -325,12 +325,49 @@ kvq_publish_small(const unsigned int *__restrict__ small, const unsigned int *__
     __threadfence_system();
 }
 
+// ---- the records of the hits (kernels_records.hip) ------------------------------------------------------------------------
+static KvqRecTable rec_table(const kvq_scan *s)
+{
+    KvqRecTable T;
+    T.key = s->d_rkey.as<unsigned long long>(); T.off = s->d_roff.as<unsigned long long>(); T.len = s->d_rlen.as<unsigned int>();
+    T.dir = s->d_rdir.as<unsigned int>(); T.ctr = s->d_rsmall.as<unsigned long long>();
+    T.store = s->d_rstore.as<uint8_t>(); T.store_cap = s->rstore_cap; T.mask = s->rslots - 1u;
+    return T;
+}
+
+// the table and the store empty, the table sized for the arena as it is now (it grows only between scans: the arena does)
+static int records_prepare(kvq_scan *s)
+{
+    int rc;
+    uint64_t slots = 1024; while (slots < 2ull * s->arena_cap) slots <<= 1;
+    if (s->rstore_cap == 0) {
+        // KVQ_RECORD_CAP=<bytes>: a smaller first store (the tests force the grow-and-rescan path with it)
+        unsigned long long cap = 32ull << 20;
+        if (const char *e = getenv("KVQ_RECORD_CAP")) { const long long v = atoll(e); if (v >= 0 && (unsigned long long)v < cap) cap = (unsigned long long)v; }
+        if ((rc = s->d_rstore.ensure((size_t)std::max<unsigned long long>(cap, 256) + 64))) return rc;
+        s->rstore_cap = cap;
+    }
+    if ((rc = s->d_rsmall.ensure(256))) return rc;
+    if (slots > s->rslots) {
+        if ((rc = s->d_rkey.ensure((size_t)slots * 8)) || (rc = s->d_roff.ensure((size_t)slots * 8)) ||
+            (rc = s->d_rlen.ensure((size_t)slots * 4)) || (rc = s->d_rdir.ensure((size_t)slots * 4))) return rc;
+        KVQ_HIP(hipMemsetAsync(s->d_rkey.p, 0, (size_t)slots * 8, s->stream));
+        s->rslots = (uint32_t)slots;
+    } else {
+        hipLaunchKernelGGL(kvq_records_clear, dim3(256), dim3(256), 0, s->stream, rec_table(s));
+    }
+    KVQ_HIP(hipMemsetAsync(s->d_rsmall.p, 0, 256, s->stream));
+    KVQ_HIP(hipGetLastError());
+    return KVQ_OK;
+}
+
 static int reset_device_state(kvq_scan *s)
 {
     static_assert(SMALL_BYTES % 8 == 0, "kvq_reset_state writes 8-byte words");
     hipLaunchKernelGGL(kvq_reset_state, dim3(256), dim3(256), 0, s->stream, (unsigned long long *)s->d_small.p, SMALL_BYTES / 8,
                        s->d_ctr, (size_t)s->t->ctr_len, s->d_covdiff.as<unsigned long long>(), (size_t)s->t->bases + (size_t)s->t->nseq + 1);
     KVQ_HIP(hipGetLastError());
+    if (s->records_on) return records_prepare(s);
     return KVQ_OK;
 }
 
@@ -479,7 +516,8 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
     for (int i = 0; i < 2; i++) if (s->ev_copy[i]) (void)hipEventDestroy(s->ev_copy[i]);
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
     if (s->ev_chain) (void)hipEventDestroy(s->ev_chain);
-    DevBuf *bufs[] = { &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_skipped, &s->d_chunk_off, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
+    if (s->pin_rec) pinned_give(s->pin_rec, s->pin_rec_cap);
+    DevBuf *bufs[] = { &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_skipped, &s->d_chunk_off, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
                        &s->d_rec_start, &s->d_read_off, &s->d_read_len, &s->d_arena, &s->d_blob, &s->d_small, &s->d_stage, &s->d_stage_b };
     for (DevBuf *b : bufs) b->release();
     s->pool.release();
@@ -489,6 +527,33 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
 
 extern "C" int32_t kvq_scan_path(const kvq_scan *s) { return s->path_bits; }
 extern "C" void kvq_scan_force_exhaustive(kvq_scan *s, int32_t on) { s->force_exhaustive = on != 0; }
+
+extern "C" int32_t kvq_scan_set_records(kvq_scan *s, int32_t on)
+{
+    kvq_clear_error();
+    if (!s->batches.empty() || s->copied_pending || s->host_pending >= 0) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_records: only before the first batch or after kvq_scan_reset");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (on && s->comm) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "records are not gathered across ranks: a scan with a communicator cannot keep them");
+        return KVQ_ERR_RUNTIME;
+    }
+    const bool was = s->records_on;
+    s->records_on = on != 0;
+    s->rec_store_bytes = 0;
+    return s->records_on && !was ? records_prepare(s) : KVQ_OK;
+}
+extern "C" const uint8_t *kvq_scan_record_blob(const kvq_scan *s)
+{
+    return s->records_on && s->finished ? s->pin_rec + 256 + ((s->rec_hcap * 8 + 255) & ~255ull) + ((s->rec_hcap * 4 + 255) & ~255ull) : nullptr;
+}
+extern "C" const int64_t *kvq_scan_hit_record_off(const kvq_scan *s) { return s->records_on && s->finished ? reinterpret_cast<const int64_t *>(s->pin_rec + 256) : nullptr; }
+extern "C" const int32_t *kvq_scan_hit_record_len(const kvq_scan *s)
+{
+    return s->records_on && s->finished ? reinterpret_cast<const int32_t *>(s->pin_rec + 256 + ((s->rec_hcap * 8 + 255) & ~255ull)) : nullptr;
+}
+extern "C" int64_t kvq_scan_record_bytes(const kvq_scan *s) { return s->records_on && s->finished ? s->rec_store_bytes : 0; }
 
 extern "C" int32_t kvq_scan_reset(kvq_scan *s)
 {
@@ -683,6 +748,9 @@ static int run_batch(kvq_scan *s, const uint8_t *d_data, int64_t nbytes, const i
         KVQ_HIP(hipMemcpyAsync(s->d_range + batch_no + 1, s->d_arena_n, 4, hipMemcpyDeviceToDevice, s->stream));
     hipLaunchKernelGGL(kvq_fold_batch, dim3(512), dim3(256), 0, s->stream, P, d_data, fpos_base,
                        (const unsigned int *)(s->d_range + batch_no), (const unsigned int *)(s->d_range + batch_no + 1));
+    if (s->records_on)
+        hipLaunchKernelGGL(kvq_gather_records, dim3(512), dim3(256), 0, s->stream, rec_table(s), (const KvqHit *)P.arena, P.arena_cap, d_data,
+                           nbytes, fpos_base, d_co, (uint32_t)nchunks, (const unsigned int *)(s->d_range + batch_no), (const unsigned int *)(s->d_range + batch_no + 1));
     KVQ_HIP(hipEventRecord(s->ev_all.back().second, s->stream));
     KVQ_HIP(hipGetLastError());
     if (g_timing) fprintf(stderr, "run_batch host %.3f ms\n", now_ms() - tb0);
@@ -852,6 +920,83 @@ extern "C" int32_t kvq_scan_host(kvq_scan *s, const void *h_data, int64_t nbytes
 // to fetch.  finish_once waits for it ONCE; kvq_scan_finish_begin enqueues it ahead of time (a job whose batches are all fed), so that
 // a caller with several jobs in flight finds it done when it comes to kvq_scan_finish -- otherwise the host sits out the ordering
 // kernels of every small job before it enqueues the next one, and those kernels run beside another job's scan at a tenth of their speed.
+// the records' part of the tail: the (offset, length) of every hit's record in canonical order, and copies of the record
+// words, of as many of those as the last scan of this handle had and of as many store bytes (finish_records fetches the rest)
+static int records_tail(kvq_scan *s, const KvqFinishState *d_st)
+{
+    int rc;
+    const size_t hoff = ((size_t)s->arena_cap * 8 + 255) & ~(size_t)255;
+    if ((rc = s->d_rres.ensure(hoff + (size_t)s->arena_cap * 4 + 256))) return rc;
+    long long *d_off = s->d_rres.as<long long>();
+    int32_t *d_len = reinterpret_cast<int32_t *>(s->d_rres.as<uint8_t>() + hoff);
+    hipLaunchKernelGGL(kvq_record_lookup, dim3(256), dim3(256), 0, s->stream, rec_table(s), d_st, (const uint8_t *)s->d_result.p, d_off, d_len);
+    KVQ_HIP(hipGetLastError());
+    s->rec_tail_n = s->rec_tail_b = 0;
+    if (!s->pin_rec) return KVQ_OK;                  // (the first finish of this handle: fetched there)
+    const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(s->rec_spec_n, s->rec_hcap), s->arena_cap);
+    const uint64_t b = std::min<uint64_t>(std::min<uint64_t>(s->rec_spec_b, s->rec_scap), s->rstore_cap);
+    uint8_t *h_len = s->pin_rec + 256 + ((s->rec_hcap * 8 + 255) & ~255ull), *h_blob = h_len + ((s->rec_hcap * 4 + 255) & ~255ull);
+    if (n) {
+        KVQ_HIP(hipMemcpyAsync(s->pin_rec + 256, d_off, n * 8, hipMemcpyDeviceToHost, s->stream));
+        KVQ_HIP(hipMemcpyAsync(h_len, d_len, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    if (b) KVQ_HIP(hipMemcpyAsync(h_blob, s->d_rstore.p, b, hipMemcpyDeviceToHost, s->stream));
+    s->rec_tail_n = n; s->rec_tail_b = b;
+    return KVQ_OK;
+}
+
+// after the tail has been waited for: did the store hold the scan's records?  A store too small (or a table that went round)
+// is grown to what the scan needed and the scan asked to go again, like an overflowing hit blob
+static int records_check(kvq_scan *s, uint64_t n_hits, unsigned long long *used, bool *grow)
+{
+    *grow = false;
+    unsigned long long w[4] = { 0, 0, 0, 0 };
+    KVQ_HIP(hipMemcpyAsync(w, s->d_rsmall.p, 32, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipStreamSynchronize(s->stream));
+    *used = w[0];
+    if (w[0] <= s->rstore_cap && !w[2]) return KVQ_OK;
+    // (hits that did not fit the arena were never gathered: scale by them, as for the hit blob)
+    unsigned long long want = w[0];
+    if (n_hits > s->arena_cap && s->arena_cap) want = (unsigned long long)((double)w[0] * ((double)n_hits / s->arena_cap) * 1.25) + (1 << 20);
+    want = std::max<unsigned long long>(want + want / 8, s->rstore_cap);
+    if (want > 0xFFFFFFF0ull) { kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
+    int rc; if ((rc = s->d_rstore.ensure((size_t)want + 64))) return rc;
+    s->rstore_cap = want;
+    *grow = true;
+    return KVQ_OK;
+}
+
+// the hits are in their final order: what the tail did not fetch of the record words and the store
+static int records_fetch(kvq_scan *s, uint64_t n_hits, unsigned long long used)
+{
+    const size_t hoff = ((size_t)s->arena_cap * 8 + 255) & ~(size_t)255;
+    bool all = false;
+    if (!s->pin_rec || n_hits > s->rec_hcap || used > s->rec_scap) {
+        const uint64_t hc = std::max<uint64_t>(n_hits + n_hits / 4 + 4096, s->rec_hcap), sc = std::max<uint64_t>(used + used / 4 + (1 << 20), s->rec_scap);
+        const size_t want = 256 + ((hc * 8 + 255) & ~255ull) + ((hc * 4 + 255) & ~255ull) + sc;
+        size_t got = 0; uint8_t *np = (uint8_t *)pinned_take(want, &got);
+        if (!np) { kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
+        if (s->pin_rec) pinned_give(s->pin_rec, s->pin_rec_cap);
+        s->pin_rec = np; s->pin_rec_cap = got; s->rec_hcap = hc; s->rec_scap = sc;
+        all = true;
+    }
+    uint8_t *h_len = s->pin_rec + 256 + ((s->rec_hcap * 8 + 255) & ~255ull), *h_blob = h_len + ((s->rec_hcap * 4 + 255) & ~255ull);
+    bool copied = false;
+    if (n_hits && (all || n_hits > s->rec_tail_n)) {
+        KVQ_HIP(hipMemcpyAsync(s->pin_rec + 256, s->d_rres.p, n_hits * 8, hipMemcpyDeviceToHost, s->stream));
+        KVQ_HIP(hipMemcpyAsync(h_len, s->d_rres.as<uint8_t>() + hoff, n_hits * 4, hipMemcpyDeviceToHost, s->stream));
+        copied = true;
+    }
+    if (used && (all || used > s->rec_tail_b)) {
+        KVQ_HIP(hipMemcpyAsync(h_blob, s->d_rstore.p, used, hipMemcpyDeviceToHost, s->stream));
+        copied = true;
+    }
+    if (copied) KVQ_HIP(hipStreamSynchronize(s->stream));
+    s->rec_store_bytes = (int64_t)used;
+    s->rec_spec_n = n_hits + n_hits / 8 + 4096; s->rec_spec_b = used + used / 8 + 65536;
+    return KVQ_OK;
+}
+
 static int enqueue_tail(kvq_scan *s)
 {
     int rc;
@@ -886,6 +1031,7 @@ static int enqueue_tail(kvq_scan *s)
         hipLaunchKernelGGL(kvq_cov_apply, dim3((uint32_t)((t->nseq + 3) / 4)), dim3(256), 0, s->stream, make_params(s));
     if (!no_buckets &&
         (rc = kvq_order_by_buckets(s->stream, s->d_arena.as<KvqHit>(), s->d_blob.as<uint8_t>(), s->blob_cap, d_st, W, s->d_result.as<uint8_t>()))) return rc;
+    if (s->records_on && (rc = records_tail(s, d_st))) return rc;
     hipLaunchKernelGGL(kvq_publish_small, dim3(1), dim3(256), 0, s->stream, (const unsigned int *)s->d_small.p,
                        (const unsigned int *)s->d_fail, (unsigned int)nb0, (const unsigned int *)d_st, (unsigned int)(sizeof(KvqFinishState) / 4),
                        (unsigned int *)small, fail, (unsigned int *)(s->pin_small + 64 + 4 * (size_t)KVQ_MAX_BATCHES));
@@ -957,6 +1103,8 @@ static int finish_once(kvq_scan *s)
             else kvq_set_error(KVQ_ERR_FORMAT, "3rd line of record must start with '+' fpos=%ld", fpos);
             return KVQ_ERR_FORMAT;
         }
+        unsigned long long rec_used = 0; bool rec_grow = false;
+        if (s->records_on && (rc = records_check(s, n_hits, &rec_used, &rec_grow))) return rc;
         if (n_hits > s->arena_cap || blob_n > s->blob_cap) {
             // grow to what this scan needs and ask for a rescan
             const uint64_t want_hits = std::max<uint64_t>(n_hits + n_hits / 8 + 1024, s->arena_cap);
@@ -967,6 +1115,7 @@ static int finish_once(kvq_scan *s)
             rc = ensure_arena(s, want_hits, want_blob); if (rc) return rc;
             return KVQ_NEED_RESCAN;
         }
+        if (rec_grow) return KVQ_NEED_RESCAN;
         const KvqResultLayout L = st.L;
         if (ctr_b + L.total > s->pin_cap) {
             // (a larger landing buffer: the counters, already there, move over)
@@ -983,11 +1132,14 @@ static int finish_once(kvq_scan *s)
             if ((rc = kvq_order_by_mergesort(s->stream, s->d_arena.as<KvqHit>(), n_hits, s->d_blob.as<uint8_t>(), s->blob_cap, d_st,
                                              s->d_sort_tmp, s->d_sorted, s->d_result.as<uint8_t>()))) return rc;
             refetch = true;
+            if (s->records_on && (rc = records_tail(s, d_st))) return rc;      // (the records follow the hits' new order: fetched again below)
+            s->rec_tail_n = 0;
         }
         if (n_hits && refetch) {
             KVQ_HIP(hipMemcpyAsync(s->pin + ctr_b, s->d_result.p, L.total, hipMemcpyDeviceToHost, s->stream));
             KVQ_HIP(hipStreamSynchronize(s->stream));
         }
+        if (s->records_on && (rc = records_fetch(s, n_hits, rec_used))) return rc;
         memcpy(s->h_ctr.data(), s->pin, (size_t)t->ctr_len * 8);
         s->pin_res = s->pin + ctr_b;
         if (!n_hits) memset(s->pin_res + L.hitseq_off, 0, 8);

@@ -5,6 +5,7 @@
 #include "kernels_bp.hip"
 #include "kvq_launch.hip"
 #include "kernels_results.hip"
+#include "kernels_records.hip"
 #include "synth.hip"
 #include "kvq_runtime.hip"
 #include "kernels_inflate.hip"

@@ -111,7 +111,7 @@ PATH_DEVICE_INFLATE = 0x10                         # kvq_scan_path bit 4
 PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
 
 
-def findseqs(fname, sequences, *, inflate='host'):
+def findseqs(fname, sequences, *, inflate='host', records=False):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
@@ -125,7 +125,12 @@ def findseqs(fname, sequences, *, inflate='host'):
     ``.gz``, each is inflated on the GPU -- a BGZF file by its blocks, any other gzip by
     speculative chunk decoding --; otherwise the call is the default
     one.  last_inflate() tells which route ran, last_inflate_report() what the
-    speculative route did."""
+    speculative route did.
+
+    records=True (not in the reference): the dict gains 'records', one entry per hit
+    (``str`` or ``bytes`` as for 'hitseqs'): the raw bytes of the FastQ record whose
+    bases line holds the hit's file_pos, identifier line to quality line, its final
+    newline included -- gathered on the GPU during the scan."""
     import os, time
     global _last_inflate
     if inflate not in INFLATE_FLAGS:
@@ -166,10 +171,10 @@ def findseqs(fname, sequences, *, inflate='host'):
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
-    if inflate == 'host':
+    if inflate == 'host' and not records:
         h = L.kvq_findseqs(farr, len(bfiles), sarr, lens, n)
     else:
-        h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate])
+        h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0))
     t_1 = time.perf_counter()
     try:
         if h:
@@ -202,7 +207,10 @@ def findseqs(fname, sequences, *, inflate='host'):
         if os.environ.get('KVQ_TIMING'):
             import sys
             sys.stderr.write('engine.findseqs: arguments %.1f ms, library %.1f ms, results as Python objects %.1f ms\n' % ((t_0 - t_in) * 1e3, (t_1 - t_0) * 1e3, (time.perf_counter() - t_1) * 1e3))
-        return {'hits': hits, 'stats': st, 'hitseqs': hitseqs}
+        out = {'hits': hits, 'stats': st, 'hitseqs': hitseqs}
+        if records:
+            out['records'] = _records(L, h, nh, as_str)
+        return out
     finally:
         if h:
             t_f = time.perf_counter()
@@ -210,6 +218,18 @@ def findseqs(fname, sequences, *, inflate='host'):
             if os.environ.get('KVQ_TIMING'):
                 import sys
                 sys.stderr.write('engine.findseqs: free %.1f ms\n' % ((time.perf_counter() - t_f) * 1e3))
+
+
+def _records(L, h, nh, as_str):
+    """the records of a finished scan object's hits (kvq_scan_hit_record_off / _len into kvq_scan_record_blob)"""
+    if not nh:
+        return []
+    off = np.ctypeslib.as_array(L.kvq_scan_hit_record_off(h), shape=(nh,)).tolist()
+    ln = np.ctypeslib.as_array(L.kvq_scan_hit_record_len(h), shape=(nh,)).tolist()
+    blob = C.string_at(L.kvq_scan_record_blob(h), L.kvq_scan_record_bytes(h))
+    if as_str:
+        blob = blob.decode('latin-1')
+    return [blob[a:a + b] for a, b in zip(off, ln)]
 
 
 def last_inflate():

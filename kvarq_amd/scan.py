@@ -96,11 +96,14 @@ class Scanner(object):
     ``finish`` raises ``RescanRequired`` and the caller, who has the data, resets and feeds again; a caller with
     a re-readable source passes ``replay=callable`` (called with the scanner after ``reset()``) instead."""
 
-    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None):
+    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False):
         self.table = table
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
+        self.records = bool(records)     # keep the FastQ record of every hit (kvq_scan_set_records; kept across reset)
+        if self.records:
+            _check(_lib.lib().kvq_scan_set_records(self.h, 1))
         self._host_batches = []          # copies of what scan_host was given since the last reset (fed again when the hit arena overflows)
         self._device_batches = []        # what scan_device was given since the last reset (the caller's device memory: nothing is copied)
         self._retained, self._retain_limit, self._replay = 0, (0 if replay is not None else retain_limit), replay
@@ -183,6 +186,8 @@ class Scanner(object):
         out['n_hits'] = L.kvq_scan_n_hits(self.h)
         if hits:
             out.update(self._hits_dict())
+            if self.records:
+                out['records'] = self._records()
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
@@ -216,7 +221,25 @@ class Scanner(object):
                                (L.kvq_scan_hit_readlength, C.c_int32, np.int32))]
         off = _view(L.kvq_scan_hitseq_offsets(self.h), nh + 1, C.c_int64, np.int64).copy()
         blob = np.frombuffer(C.string_at(L.kvq_scan_hitseq_blob(self.h), int(off[nh])) if nh else b'', dtype=np.uint8)
-        return dict(seq_nr=a[0], file_pos=a[1], seq_pos=a[2], length=a[3], readlength=a[4], offsets=off, blob=blob)
+        out = dict(seq_nr=a[0], file_pos=a[1], seq_pos=a[2], length=a[3], readlength=a[4], offsets=off, blob=blob)
+        if self.records:
+            # hit i's record: record_blob[record_off[i] : record_off[i] + record_len[i]]
+            out['record_off'] = _view(L.kvq_scan_hit_record_off(self.h), nh, C.c_int64, np.int64).copy()
+            out['record_len'] = _view(L.kvq_scan_hit_record_len(self.h), nh, C.c_int32, np.int32).copy()
+            nb = L.kvq_scan_record_bytes(self.h)
+            out['record_blob'] = np.frombuffer(C.string_at(L.kvq_scan_record_blob(self.h), nb) if nb else b'', dtype=np.uint8)
+        return out
+
+    def _records(self):
+        """the record of every hit (bytes), in the order of ``hits``"""
+        L = _lib.lib()
+        nh = L.kvq_scan_n_hits(self.h)
+        if not nh:
+            return []
+        off = _view(L.kvq_scan_hit_record_off(self.h), nh, C.c_int64, np.int64).tolist()
+        ln = _view(L.kvq_scan_hit_record_len(self.h), nh, C.c_int32, np.int32).tolist()
+        blob = C.string_at(L.kvq_scan_record_blob(self.h), L.kvq_scan_record_bytes(self.h))
+        return [blob[a:a + b] for a, b in zip(off, ln)]
 
     def _hits_dict(self):
         """the library's result arrays as the reference's ``hits`` tuple and ``hitseqs`` list"""
