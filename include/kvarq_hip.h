@@ -209,7 +209,7 @@ int32_t kvq_scan_reset(kvq_scan *s);
  * bit 3 = tiles of the seed-filter pass left their records alone (a record longer than a tile's
  * look-ahead, more newlines than its tables hold) and those records were scanned again, bit 4 = the text was inflated
  * on the device (kvq_findseqs_ex, KVQ_FIND_DEVICE_INFLATE or KVQ_FIND_DEVICE_GZIP), bit 5 = a file of it took the speculative
- * route of KVQ_FIND_DEVICE_GZIP */
+ * route of KVQ_FIND_DEVICE_GZIP, bit 6 = the text was decoded from BAM on the device (kvq_findseqs on BAM files) */
 int32_t kvq_scan_path(const kvq_scan *s);
 /* 0 = let the table decide, 1 = force the exhaustive kernel for every sequence */
 void    kvq_scan_force_exhaustive(kvq_scan *s, int32_t on);
@@ -440,6 +440,49 @@ void    kvq_gzip_last_report(kvq_gzip_report *rep);
 int64_t kvq_gzip_slot_canaries(int32_t pad_symbols);
 int64_t kvq_gzip_last_chunks(int64_t *cand, int64_t ncand_cap, int64_t *start_bit, int64_t *end_bit, int64_t *nsym, int64_t cap,
                              int64_t *ncand);
+
+/* ---- BAM records as FastQ text -------------------------------------------------------------------
+ * kvq_findseqs and kvq_findseqs_ex scan a BAM file (its first BGZF block inflates to "BAM\1"; the name does not matter) as
+ * its *virtual FastQ text*: every primary record with bases, in file order, as
+ *   '@' name ["/1" | "/2" by flag & 0xC0] '\n' bases '\n' '+' '\n' qualities '\n'
+ * bases "=ACMGRSVTWYHKDBN"[code], qualities q + 33 ('"' for every base when qualities are absent), both reversed and the
+ * bases complemented for flag 0x10; records with flag & 0x900 or l_seq == 0 write nothing.  Hits, counters, stats (but
+ * total), records: those of a scan of that text; file_pos counts its bytes.  The text is made on the GPU only: a call whose
+ * files are all BAM takes that route whatever the flags say (kvq_scan_path bit 6), one that mixes BAM and other files fails
+ * with KVQ_ERR_IO.  A record is well-formed when l_read_name >= 2, its name is printable and NUL-terminated, refID and
+ * next_refID lie in [-1, n_ref), pos and next_pos >= -1, l_seq >= 0, 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 +
+ * l_seq <= block_size and the record ends inside the file's inflated stream; the first that is not gives KVQ_ERR_IO
+ * "malformed BAM record : offset=<its offset in the file's inflated stream>". */
+typedef struct kvq_bam_report {
+    int64_t runs;               /* runs of whole BGZF blocks (one per call of kvq_bam_to_fastq_device) */
+    int64_t segments;           /* segments the runs were cut into (KVQ_BAM_SEGMENT_KB) */
+    int64_t refuted;            /* segments the chain check walked again (a false start, or one behind a false one) */
+    int64_t check_passes;       /* passes of the chain check, the first one of each run included */
+    int64_t records_seen;       /* records on the chain */
+    int64_t records_written;    /* ... that wrote text */
+    int64_t records_skipped;    /* ... that did not (flag & 0x900, l_seq == 0) */
+    int64_t records_noqual;     /* written records without qualities (qual[0] == 0xFF) */
+    int64_t bam_bytes;          /* inflated BAM bytes, headers included */
+    int64_t text_bytes;         /* FastQ bytes written */
+    double  ms_inflate, ms_find, ms_emit;   /* wall time of the phases (each ends in a wait for its kernels; find includes the
+                                               chain check's passes) */
+} kvq_bam_report;
+/* the report of the last kvq_bam_to_fastq_* call or kvq_findseqs call that scanned BAM */
+void    kvq_bam_last_report(kvq_bam_report *rep);
+/* host only: the header at the front of a file's inflated bytes; returns the first record's offset and *n_ref, -1 when the
+ * header is malformed, -2 when the n bytes end inside it */
+int64_t kvq_bam_header_host(const uint8_t *inflated, int64_t n, int32_t *n_ref);
+/* on the CPU (the twin of the GPU route, over the same source): the virtual FastQ text of the records in inflated[first_record, n),
+ * n being the end of the file's inflated stream.  Returns the text's length -- written to out only when it fits cap --, or -1
+ * at the first malformed record (*consumed: its offset; kvq_last_error: the route's message), -2 on bad arguments.  *consumed
+ * (may be NULL): where the walk stopped */
+int64_t kvq_bam_to_fastq_host(const uint8_t *inflated, int64_t n, int32_t n_ref, int64_t first_record, uint8_t *out, int64_t cap,
+                              int64_t *consumed);
+/* on the GPU, the route's kernels alone: d_in[0, n) and d_out in device memory, segment_bytes (0: KVQ_BAM_SEGMENT_KB, else
+ * 1 .. 64 MiB).  Returns the text's length -- written to d_out only when it fits cap --, -1 at the first malformed record
+ * (kvq_last_error as above), -2 on other errors.  Blocking; *report (may be NULL) as kvq_bam_last_report */
+int64_t kvq_bam_to_fastq_device(const void *d_in, int64_t n, int32_t n_ref, int64_t first_record, void *d_out, int64_t cap,
+                                int64_t segment_bytes, kvq_bam_report *report);
 
 const char *kvq_version(void);
 

@@ -34,6 +34,15 @@ class GzipReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BamReport(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ('runs', 'segments', 'refuted', 'check_passes', 'records_seen', 'records_written',
+                                         'records_skipped', 'records_noqual', 'bam_bytes', 'text_bytes')] + \
+        [(n, C.c_double) for n in ('ms_inflate', 'ms_find', 'ms_emit')]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 i32, i64, u64, vp, cp = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p, C.c_char_p
 P = C.POINTER
 
@@ -134,6 +143,10 @@ PROTOTYPES = {
     'kvq_gzip_last_report': (None, [P(GzipReport)]),
     'kvq_gzip_slot_canaries': (i64, [i32]),
     'kvq_gzip_last_chunks': (i64, [P(i64), i64, P(i64), P(i64), P(i64), i64, P(i64)]),
+    'kvq_bam_last_report': (None, [P(BamReport)]),
+    'kvq_bam_header_host': (i64, [vp, i64, P(i32)]),
+    'kvq_bam_to_fastq_host': (i64, [vp, i64, i32, i64, vp, i64, P(i64)]),
+    'kvq_bam_to_fastq_device': (i64, [vp, i64, i32, i64, vp, i64, i64, P(BamReport)]),
     'kvq_version': (cp, []),
 }
 

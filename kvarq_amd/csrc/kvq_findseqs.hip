@@ -1148,16 +1148,216 @@ static int stream_gzip_device(Sink &sink, kvq_scan *s, const std::vector<GzFile>
     return KVQ_OK;
 }
 
+// ---------------------------------------------------------------------------
+// BAM files, decoded to their virtual FastQ text on the device
+// ---------------------------------------------------------------------------
+
+struct BamFile { std::string name; int64_t size = 0, isize = 0, first = 0; int32_t n_ref = 0; std::vector<kvq_bgzf_entry_> blocks; };
+
+// 1 when the file starts with a BGZF block whose inflated bytes begin with "BAM\1" (inflated only as far as that), 0 when not,
+// -1 when the file cannot be opened
+static int bam_peek(const char *name)
+{
+    FILE *fd = fopen(name, "rb");
+    if (!fd) return -1;
+    fseek(fd, 0, SEEK_END); const int64_t size = ftell(fd);
+    const int fdn = fileno(fd);
+    auto read = [&](uint8_t *dst, int64_t k, int64_t at) -> int64_t { const ssize_t got = pread(fdn, dst, (size_t)k, (off_t)at); return got < 0 ? 0 : (int64_t)got; };
+    kvq_bgzf_entry_ b;
+    int is = 0;
+    if (kvq_bgzf_peek(read, size, 0, &b) && b.isize >= 4) {
+        uint8_t in[4096], out[4];
+        const int64_t k = std::min<int64_t>(b.size - b.hdr - 8, sizeof(in));
+        z_stream z; memset(&z, 0, sizeof(z));
+        if (read(in, k, b.hdr) == k && inflateInit2(&z, -MAX_WBITS) == Z_OK) {
+            z.next_in = in; z.avail_in = (uInt)k; z.next_out = out; z.avail_out = 4;
+            (void)inflate(&z, Z_SYNC_FLUSH);
+            is = z.avail_out == 0 && out[0] == 'B' && out[1] == 'A' && out[2] == 'M' && out[3] == 1;
+            inflateEnd(&z);
+        }
+    }
+    fclose(fd);
+    return is;
+}
+
+// every file's blocks (BGZF to its end, else "truncated BAM file") and header (inflated block after block on the host until it
+// is whole, else "malformed BAM header")
+static int bam_files(const char *const *files, int nfiles, std::vector<BamFile> &out)
+{
+    out.clear();
+    for (int i = 0; i < nfiles; i++) {
+        BamFile f; f.name = files[i];
+        FILE *fd = fopen(f.name.c_str(), "rb");
+        if (!fd) { kvq_set_error(KVQ_ERR_IO, "cannot open file"); return KVQ_ERR_IO; }
+        struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{ fd };
+        fseek(fd, 0, SEEK_END); f.size = ftell(fd);
+        const int fdn = fileno(fd);
+        auto read = [&](uint8_t *dst, int64_t k, int64_t at) -> int64_t { const ssize_t got = pread(fdn, dst, (size_t)k, (off_t)at); return got < 0 ? 0 : (int64_t)got; };
+        if (!kvq_bgzf_walk(read, f.size, f.blocks)) { kvq_set_error(KVQ_ERR_IO, "truncated BAM file"); return KVQ_ERR_IO; }
+        for (auto &b : f.blocks) f.isize += b.isize;
+        std::vector<uint8_t> head, comp;
+        int64_t first = -2;
+        for (size_t k = 0; k < f.blocks.size() && first == -2; k++) {
+            const kvq_bgzf_entry_ &b = f.blocks[k];
+            comp.resize(b.size);
+            if (read(comp.data(), b.size, b.off) != (int64_t)b.size) { kvq_set_error(KVQ_ERR_IO, "truncated BAM file"); return KVQ_ERR_IO; }
+            const size_t at = head.size();
+            head.resize(at + b.isize);
+            const int st = kvq_inflate_raw_host(comp.data() + b.hdr, b.size - b.hdr - 8, head.data() + at, b.isize);
+            if (st) { kvq_set_error(KVQ_ERR_IO, "error while inflating compressed data : status=%d fpos=%ld", st, (long)at); return KVQ_ERR_IO; }
+            first = kvq_bam_header(head.data(), (int64_t)head.size(), &f.n_ref);
+        }
+        if (first < 0) { kvq_set_error(KVQ_ERR_IO, "malformed BAM header"); return KVQ_ERR_IO; }
+        f.first = first;
+        out.push_back(std::move(f));
+    }
+    return KVQ_OK;
+}
+
+// The walk of stream_device for BAM files: per run of whole blocks, kvq_inflate_bgzf into a BAM buffer behind the record the
+// run before ended inside (the two BAM buffers alternate), the records found and checked (bam_run_find), their text written
+// behind the unfinished chunk (bam_run_emit), then the cuts and the scan as stream_device makes them.  file_pos and parsed count
+// text bytes; the estimate of the total is the host reader's with text bytes for inflated ones.
+template <class Sink>
+static int stream_bam_device(Sink &sink, kvq_scan *s, const std::vector<BamFile> &files, int64_t *parsed, int64_t *total_out)
+{
+    int rc;
+    int64_t size_all = 0;
+    for (auto &f : files) size_all += f.size;
+    sink.begin(size_all);
+    const int64_t batch_cap = device_batch_bytes(), seg_bytes = bam_segment_bytes_default();
+    if ((rc = g_dev.d_cut.ensure((8 + KVQ_CUT_CAP) * 8))) return rc;
+    if ((rc = pinned_grow(&g_dev.pcut, &g_dev.pcut_cap, (8 + KVQ_CUT_CAP) * 8))) return rc;
+    kvq_config cfg; kvq_config_get(&cfg);
+    hipStream_t st = s->stream;
+    kvq_bam_report &rep = g_bam_report;
+    rep = kvq_bam_report();
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    struct Events { hipEvent_t *e; ~Events() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } events{ ev };
+    for (int i = 0; i < 4; i++) KVQ_HIP(hipEventCreate(&ev[i]));
+
+    int64_t fpos = 0, ftell0 = 0, total = size_all;
+    int tb = 0, bb = 0;
+    for (size_t fi = 0; fi < files.size() && !g_stop.load(); fi++) {
+        const BamFile &F = files[fi];
+        FILE *fd = fopen(F.name.c_str(), "rb");
+        if (!fd) { kvq_set_error(KVQ_ERR_IO, "cannot open file"); return KVQ_ERR_IO; }
+        struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{ fd };
+        const auto &bl = F.blocks;
+        int64_t carry = 0, carry_src = 0, fill = 0, text_fpos = fpos, consumed = 0;      // the unfinished chunk (text buffer cb)
+        int64_t bcarry = 0, bcarry_src = 0, run_base = 0, skip = F.first;                // the unfinished record (BAM buffer bb ^ 1)
+        int cb = tb;
+        // runs of whole blocks: [b0, b1) is read into pinned slot `slot`; the next one is read while the GPU inflates it
+        auto run_end = [&](size_t from) { size_t e = from; int64_t z = 0; while (e < bl.size() && (e == from || z + bl[e].isize <= batch_cap)) z += bl[e++].isize; return e; };
+        auto read_run = [&](size_t from, size_t to, int sl) -> int {
+            const int64_t a = bl[from].off, e = bl[to - 1].off + bl[to - 1].size;
+            int rc2 = pinned_grow(&g_dev.pin[sl], &g_dev.pin_cap[sl], (size_t)(e - a));
+            if (rc2) return rc2;
+            if (!pread_run(fileno(fd), (uint8_t *)g_dev.pin[sl], e - a, a, cfg.nthreads)) {
+                kvq_set_error(KVQ_ERR_IO, "could not read enough bytes from .fastq.gz : I/O error"); return KVQ_ERR_IO;
+            }
+            return KVQ_OK;
+        };
+        size_t b0 = 0, b1 = run_end(0);
+        int slot = 0;
+        if ((rc = read_run(b0, b1, slot))) return rc;
+        bool eof = false;
+        while (!eof && !g_stop.load()) {
+            // the run into the BAM buffer, behind the unfinished record
+            int64_t isz = 0;
+            for (size_t i = b0; i < b1; i++) isz += bl[i].isize;
+            const int64_t c1 = bl[b1 - 1].off + bl[b1 - 1].size;
+            if ((rc = g_bam.d_bam[bb].ensure((size_t)(bcarry + isz + 64)))) return rc;
+            uint8_t *bam = g_bam.d_bam[bb].as<uint8_t>();
+            int64_t n = 0;
+            KVQ_HIP(hipEventRecord(ev[0], st));
+            if ((rc = bgzf_run_enqueue(bl, b0, b1, slot, bam, (int64_t)g_bam.d_bam[bb].cap, bcarry, g_bam.d_bam[bb ^ 1].as<uint8_t>() + bcarry_src, st, &n))) return rc;
+            KVQ_HIP(hipEventRecord(ev[1], st));
+            const size_t nb0 = b1, nb1 = b1 < bl.size() ? run_end(b1) : b1;
+            if (nb1 > nb0 && (rc = read_run(nb0, nb1, slot ^ 1))) return rc;
+            KVQ_HIP(hipStreamSynchronize(st));
+            float ms = 0; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) rep.ms_inflate += ms;
+            if ((rc = bgzf_run_check(slot, (int64_t)(b1 - b0), run_base))) return rc;
+            b0 = nb0; b1 = nb1; slot ^= 1; eof = b0 == bl.size();
+            consumed = eof ? F.size : c1;
+            rep.runs++; rep.bam_bytes += isz;
+            // the records of the run and their text's size
+            const int64_t s0 = std::min(skip, n);
+            skip -= s0;
+            BamRunOut ro;
+            if ((rc = bam_run_find(bam, n, F.isize - run_base, F.n_ref, s0, seg_bytes, st, rep, ro))) return rc;
+            if (ro.err >= 0) { kvq_set_error(KVQ_ERR_IO, "malformed BAM record : offset=%ld", (long)(run_base + ro.err)); return KVQ_ERR_IO; }
+            const int64_t have = carry + ro.text;
+            if (have > (4ll << 30) - (1 << 20)) { kvq_set_error(KVQ_ERR_RUNTIME, "BAM batch of %ld text bytes (KVQ_INFLATE_BATCH_MB)", (long)have); return KVQ_ERR_RUNTIME; }
+            // the text behind the unfinished chunk (the text buffer of this run is not the one of the batch in flight)
+            if (g_dev.d_text[tb].cap < (size_t)(have + 64)) {
+                // (a run that handed nothing over left its carry at the front of this very buffer: it moves along)
+                DevBuf nb;
+                if ((rc = nb.ensure((size_t)(have + 64)))) return rc;
+                if (cb == tb && carry) KVQ_HIP(hipMemcpyAsync(nb.p, g_dev.d_text[tb].p, (size_t)carry, hipMemcpyDeviceToDevice, st));
+                KVQ_HIP(hipStreamSynchronize(st));
+                g_dev.d_text[tb].release(); g_dev.d_text[tb] = nb;
+                if (cb == tb) carry_src = 0;
+            }
+            uint8_t *text = g_dev.d_text[tb].as<uint8_t>();
+            const uint8_t *carry_at = g_dev.d_text[cb].as<uint8_t>() + carry_src;
+            if (carry && carry_at != text) KVQ_HIP(hipMemcpyAsync(text, carry_at, (size_t)carry, hipMemcpyDeviceToDevice, st));
+            KVQ_HIP(hipEventRecord(ev[2], st));
+            if ((rc = bam_run_emit(bam, s0, seg_bytes, ro, text, carry, (int64_t)g_dev.d_text[tb].cap, st))) return rc;
+            KVQ_HIP(hipEventRecord(ev[3], st));
+            rep.text_bytes += ro.text;
+            // the unfinished record goes to the front of the other BAM buffer with the next run
+            bcarry = n - ro.end; bcarry_src = ro.end; run_base += ro.end; bb ^= 1;
+            // the cuts, as stream_device makes them
+            int64_t *cut = (int64_t *)g_dev.pcut;
+            int64_t *d_cut = g_dev.d_cut.as<int64_t>();
+            std::vector<int64_t> off;
+            int64_t cs = 0, cfill = fill;
+            for (;;) {
+                if ((rc = kvq_cut_chunks_launch(text, have, cs, cfill, d_cut + 8, KVQ_CUT_CAP, d_cut, st))) return rc;
+                KVQ_HIP(hipMemcpyAsync(cut, d_cut, (8 + KVQ_CUT_CAP) * 8, hipMemcpyDeviceToHost, st));
+                KVQ_HIP(hipStreamSynchronize(st));
+                if (cut[3]) {
+                    kvq_set_error(KVQ_ERR_RUNTIME, "could find beginning of record; read %ld bytes up to %ld", (long)cut[4], (long)(text_fpos + cut[5]));
+                    return KVQ_ERR_RUNTIME;
+                }
+                off.insert(off.end(), cut + 8, cut + 8 + cut[0]);
+                cs = cut[1]; cfill = cut[2];
+                if (cut[0] < KVQ_CUT_CAP) break;
+            }
+            ms = 0; if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) rep.ms_emit += ms;
+            fill = cfill;
+            fpos += ro.text;
+            if (ftell0 + consumed > 0)
+                total = (int64_t)(size_t)((float)size_all * fpos / (ftell0 + consumed));          // the host reader's estimate (883-884)
+            if (eof) { if (have > cs) off.push_back(cs); cs = have; }
+            const bool handed = !off.empty();
+            if (handed) {
+                off.push_back(cs);
+                if ((rc = sink.batch(text, cs, off.data(), (int64_t)off.size() - 1, text_fpos, fpos, total))) return rc;
+            }
+            if (eof) { ftell0 += consumed; }
+            else { carry = have - cs; carry_src = cs; cb = tb; fill -= cs; text_fpos += cs; }
+            if (handed) tb ^= 1;
+        }
+    }
+    s->path_bits |= 64;
+    *parsed = fpos; *total_out = total;
+    return KVQ_OK;
+}
+
 // one pass over the files with the current arena; KVQ_NEED_RESCAN asks for another.  bz: the files' BGZF blocks when the
 // device-inflate route was taken
 static int findseqs_pass(kvq_scan *s, const char *const *files, int nfiles, uint8_t *pin, uint8_t *pin2, int64_t pin_cap,
-                         const std::vector<BgzfFile> *bz = nullptr, const std::vector<GzFile> *gz = nullptr)
+                         const std::vector<BgzfFile> *bz = nullptr, const std::vector<GzFile> *gz = nullptr,
+                         const std::vector<BamFile> *bam = nullptr)
 {
-    ScanSink sink; sink.s = s; sink.staged = bz != nullptr || gz != nullptr;
+    ScanSink sink; sink.s = s; sink.staged = bz != nullptr || gz != nullptr || bam != nullptr;
     int64_t parsed = 0, total = 0;
     const double tp0 = now_ms();
     int rc = bz ? stream_device(sink, s, *bz, &parsed, &total)
            : gz ? stream_gzip_device(sink, s, *gz, &parsed, &total)
+           : bam ? stream_bam_device(sink, s, *bam, &parsed, &total)
                 : stream_batches(sink, files, nfiles, pin, pin_cap, &parsed, &total, pin2);                 // two host buffers
     if (g_timing) fprintf(stderr, "findseqs pass: stream %.1f ms\n", now_ms() - tp0);
     if (rc) return rc;
@@ -1239,13 +1439,23 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
     // streaming a 1 GB file through them (only one findseqs runs at a time, g_running)
     static uint8_t *g_pin = nullptr;
     const int64_t pin_cap = BATCH_BYTES + 2 * KVQ_SCANBUFSIZE;
+    // BAM files (by their bytes, whatever the flags say): all of them take the BAM route; BAM beside other files is refused.
+    // (A file that cannot be opened leaves the decision to the other routes, which report it.)
+    std::vector<BamFile> bamf;
+    bool bam = false, bam_failed = false;
+    if (s) {
+        int nbam = 0; bool unreadable = false;
+        for (int32_t i = 0; i < nfiles; i++) { const int v = bam_peek(files[i]); unreadable |= v < 0; nbam += v > 0; }
+        if (!unreadable && nbam > 0 && nbam < nfiles) { kvq_set_error(KVQ_ERR_IO, "cannot scan BAM and FastQ files in one call"); bam_failed = true; }
+        else if (!unreadable && nbam > 0) { bam = true; bam_failed = bam_files(files, nfiles, bamf) != KVQ_OK; }
+    }
     // the device-inflate route: asked for, and every file is BGZF to its end (else the call takes the host route unchanged)
     std::vector<BgzfFile> bz;
-    const bool dev = s && (flags & (KVQ_FIND_DEVICE_INFLATE | KVQ_FIND_DEVICE_GZIP)) && bgzf_files(files, nfiles, bz);
+    const bool dev = s && !bam && !bam_failed && (flags & (KVQ_FIND_DEVICE_INFLATE | KVQ_FIND_DEVICE_GZIP)) && bgzf_files(files, nfiles, bz);
     // ... or any gzip: every file a ".gz", BGZF or not (each one takes its own way)
     std::vector<GzFile> gzf;
-    const bool dev_any = s && !dev && (flags & KVQ_FIND_DEVICE_GZIP) && gz_files(files, nfiles, gzf);
-    if (s && !dev && !dev_any && !g_pin && hipHostMalloc((void **)&g_pin, (size_t)pin_cap * 2, hipHostMallocDefault) != hipSuccess) {
+    const bool dev_any = s && !bam && !bam_failed && !dev && (flags & KVQ_FIND_DEVICE_GZIP) && gz_files(files, nfiles, gzf);
+    if (s && !bam && !bam_failed && !dev && !dev_any && !g_pin && hipHostMalloc((void **)&g_pin, (size_t)pin_cap * 2, hipHostMallocDefault) != hipSuccess) {
         kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for scanning"); g_pin = nullptr;
     }
     uint8_t *const pin = g_pin;
@@ -1256,9 +1466,10 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         if (v >= 2 && (v << 20) < BATCH_BYTES) use_cap = ((int64_t)v << 20) + 2 * KVQ_SCANBUFSIZE;
     }
     const double tf2 = now_ms();
-    if (s && (pin || dev || dev_any)) {
+    if (s && !bam_failed && (pin || dev || dev_any || bam)) {
         for (int attempt = 0; attempt < 4; attempt++) {
-            const int rc = dev ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, &bz)
+            const int rc = bam ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, nullptr, nullptr, &bamf)
+                         : dev ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, &bz)
                          : dev_any ? findseqs_pass(s, files, nfiles, nullptr, nullptr, 0, nullptr, &gzf)
                                : findseqs_pass(s, files, nfiles, pin, pin + pin_cap, use_cap);
             if (rc != KVQ_NEED_RESCAN) break;

@@ -109,6 +109,7 @@ _last_inflate = None
 INFLATE_FLAGS = {'host': 0, 'device': 1, 'device_any': 2}     # KVQ_FIND_DEVICE_INFLATE, KVQ_FIND_DEVICE_GZIP
 PATH_DEVICE_INFLATE = 0x10                         # kvq_scan_path bit 4
 PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
+PATH_DEVICE_BAM = 0x40                             # kvq_scan_path bit 6
 
 
 def findseqs(fname, sequences, *, inflate='host', records=False):
@@ -130,7 +131,15 @@ def findseqs(fname, sequences, *, inflate='host', records=False):
     records=True (not in the reference): the dict gains 'records', one entry per hit
     (``str`` or ``bytes`` as for 'hitseqs'): the raw bytes of the FastQ record whose
     bases line holds the hit's file_pos, identifier line to quality line, its final
-    newline included -- gathered on the GPU during the scan."""
+    newline included -- gathered on the GPU during the scan.
+
+    BAM files (not in the reference; recognised by their bytes, not their name) are
+    scanned as their *virtual FastQ text* (DESIGN section 12): every primary record with
+    bases as '@name[/1|/2]', bases, '+', qualities, the reverse strand restored.  Hits,
+    stats, counters and records are those of a scan of that text, and file_pos counts
+    its bytes.  The records are decoded on the GPU whatever ``inflate`` says
+    (last_inflate() == 'device_bam', last_bam_report() what the route did); a call that
+    mixes BAM and other files raises IOError."""
     import os, time
     global _last_inflate
     if inflate not in INFLATE_FLAGS:
@@ -179,7 +188,8 @@ def findseqs(fname, sequences, *, inflate='host', records=False):
     try:
         if h:
             path = L.kvq_scan_path(h)
-            _last_inflate = ('device_gzip' if path & PATH_DEVICE_GZIP else 'device' if path & PATH_DEVICE_INFLATE else 'host')
+            _last_inflate = ('device_bam' if path & PATH_DEVICE_BAM else 'device_gzip' if path & PATH_DEVICE_GZIP
+                             else 'device' if path & PATH_DEVICE_INFLATE else 'host')
         code, _ = _lib.last_error()
         if not h or code:
             _raise_last()
@@ -208,6 +218,11 @@ def findseqs(fname, sequences, *, inflate='host', records=False):
             import sys
             sys.stderr.write('engine.findseqs: arguments %.1f ms, library %.1f ms, results as Python objects %.1f ms\n' % ((t_0 - t_in) * 1e3, (t_1 - t_0) * 1e3, (time.perf_counter() - t_1) * 1e3))
         out = {'hits': hits, 'stats': st, 'hitseqs': hitseqs}
+        if _last_inflate == 'device_bam':
+            noqual = last_bam_report()['records_noqual']
+            if noqual:
+                lo.warning('%d BAM records without qualities were written with Phred 1 (\'"\'): at the default Amin '
+                           'they are trimmed to nothing' % noqual)
         if records:
             out['records'] = _records(L, h, nh, as_str)
         return out
@@ -235,8 +250,18 @@ def _records(L, h, nh, as_str):
 def last_inflate():
     """where the text of the last findseqs call was inflated: 'device' (the BGZF route on the
     GPU), 'device_gzip' (inflate='device_any' and a file took the speculative route on the GPU),
-    'host' (the reader on the CPU, plain files included), or None before any call"""
+    'device_bam' (BAM files, decoded to FastQ text on the GPU), 'host' (the reader on the CPU,
+    plain files included), or None before any call"""
     return _last_inflate
+
+
+def last_bam_report():
+    """what the BAM route did in the last call that took it (kvq_bam_report as a dict: runs, segments,
+    refuted, check_passes, records_seen / _written / _skipped / _noqual, bam_bytes, text_bytes,
+    ms_inflate, ms_find, ms_emit)"""
+    rep = _lib.BamReport()
+    _lib.lib().kvq_bam_last_report(C.byref(rep))
+    return rep.as_dict()
 
 
 def last_inflate_report():
