@@ -403,7 +403,7 @@ int64_t kvq_chunk_offsets_device(const void *d_data, int64_t nbytes, int64_t *of
  * A whole gzip file's bytes are cut into chunks of chunk_bytes (>= 64) compressed bytes; each chunk is decoded from the first
  * dynamic-Huffman block header behind its start with its 32 KiB window unknown, the chain of chunks is checked (a chunk whose
  * predecessor did not end exactly at its start is decoded again from where it did end), the windows are resolved in order and
- * the markers replaced.  The text is the host reader's (GzSerial, kvq_findseqs.hip): members crossed by its rules, a file cut
+ * the markers replaced.  The text is the host reader's (GzSerial, kvq_reader.hip): members crossed by its rules, a file cut
  * short ends the text, no CRC32 check.  Returns the text's length -- written to out only when it fits out_cap --, or -1 when
  * the DEFLATE data fail (*status: zlib's status, -3; *err_fpos: the text offset at which the failing block's output starts;
  * kvq_last_error: the host route's message), -2 on other errors (no gzip header at byte 0: the host route's message). */

@@ -124,17 +124,6 @@ static struct BamBufs {
     void *pseg = nullptr, *predo = nullptr; size_t pseg_cap = 0, predo_cap = 0;
 } g_bam;
 
-static int bam_pinned_grow(void **p, size_t *cap, size_t need)
-{
-    if (*cap >= need) return KVQ_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    const size_t want = need + need / 4;
-    if (hipHostMalloc(p, want, hipHostMallocDefault) != hipSuccess) { *p = nullptr; kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for scanning"); return KVQ_ERR_MEMORY; }
-    *cap = want;
-    return KVQ_OK;
-}
-
 // what bam_run_find learnt of a run p[0, n)
 struct BamRunOut {
     int64_t nseg = 0;
@@ -158,7 +147,7 @@ static int bam_run_find(const uint8_t *d_p, int64_t n, int64_t limit, int32_t n_
     if ((rc = g_bam.d_seg.ensure((size_t)nseg * sizeof(KvqBamSeg)))) return rc;
     if ((rc = g_bam.d_slot.ensure((size_t)(nseg * cap) * 4))) return rc;
     if ((rc = g_bam.d_toff.ensure((size_t)(nseg * cap) * 4))) return rc;
-    if ((rc = bam_pinned_grow(&g_bam.pseg, &g_bam.pseg_cap, (size_t)nseg * sizeof(KvqBamSeg)))) return rc;
+    if ((rc = pinned_grow(&g_bam.pseg, &g_bam.pseg_cap, (size_t)nseg * sizeof(KvqBamSeg)))) return rc;
     KvqBamSeg *seg = (KvqBamSeg *)g_bam.pseg;
     const double t0 = now_ms();
     hipLaunchKernelGGL(kvq_bam_find, dim3((uint32_t)nseg), dim3(KVQ_WAVE), 0, st, d_p, n, limit, n_ref, s0, seg_bytes, nseg,
@@ -187,7 +176,7 @@ static int bam_run_find(const uint8_t *d_p, int64_t n, int64_t limit, int32_t n_
         rep.refuted += (int64_t)redo.size() / 2;
         const int64_t nr = (int64_t)redo.size() / 2;
         if ((rc = g_bam.d_redo.ensure(redo.size() * 8))) return rc;
-        if ((rc = bam_pinned_grow(&g_bam.predo, &g_bam.predo_cap, redo.size() * 8))) return rc;
+        if ((rc = pinned_grow(&g_bam.predo, &g_bam.predo_cap, redo.size() * 8))) return rc;
         memcpy(g_bam.predo, redo.data(), redo.size() * 8);
         KVQ_HIP(hipMemcpyAsync(g_bam.d_seg.p, seg, (size_t)nseg * sizeof(KvqBamSeg), hipMemcpyHostToDevice, st));
         KVQ_HIP(hipMemcpyAsync(g_bam.d_redo.p, g_bam.predo, redo.size() * 8, hipMemcpyHostToDevice, st));

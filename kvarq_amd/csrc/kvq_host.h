@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <unistd.h>
 #include <vector>
 
 #include "../../include/kvarq_hip.h"
@@ -205,3 +206,15 @@ struct kvq_bgzf_entry_ { int64_t off; uint32_t size, hdr, isize; };     // a BGZ
 int kvq_inflate_bgzf_launch(const uint8_t *d_in, int64_t in_bytes, const kvq_bgzf_block *d_tab, int64_t nblocks,
                             uint8_t *d_out, int64_t out_bytes, int32_t *d_status, hipStream_t stream);
 int kvq_cut_chunks_launch(const uint8_t *d_text, int64_t have, int64_t cs, int64_t fill, int64_t *d_offs, int64_t cap, int64_t *d_res, hipStream_t stream);
+
+// kvq_findseqs.hip: engine.stop() has asked the running findseqs to end (every walk looks at every run)
+bool kvq_stop_requested();
+
+// ---- input files (kvq_routes.hip, kvq_reader.hip) ----------------------------
+// up to k bytes at offset `at` of an open file: the `read` of kvq_bgzf_peek and kvq_bgzf_walk (an error reads nothing)
+struct PreadAt {
+    int fdn;
+    int64_t operator()(uint8_t *dst, int64_t k, int64_t at) const { const ssize_t got = pread(fdn, dst, (size_t)k, (off_t)at); return got < 0 ? 0 : (int64_t)got; }
+};
+// gzip or not is decided by the name (workhorse.c:582)
+static inline bool gz_suffix(const std::string &name) { return name.size() >= 3 && name.compare(name.size() - 3, 3, ".gz") == 0; }

@@ -278,7 +278,7 @@ KVQ_HD int kvq_inflate_core(const G &g, KvqInflateWork *ws, const uint8_t *in, i
 // Plain gzip by chunks: one decoder starts at a bit offset of a whole gzip file's bytes, with the 32 KiB
 // in front of it unknown, and writes 16-bit symbols -- 0..255 a byte, KVQ_INF_MARKER + k byte k of that unknown window (a
 // back-reference copies symbols as they are, markers included).  It stops at the first block boundary at or past a bound,
-// or where the host reader's text ends, and crosses gzip members by the host reader's rules (GzSerial in kvq_findseqs.hip).
+// or where the host reader's text ends, and crosses gzip members by the host reader's rules (GzSerial in kvq_reader.hip).
 // ---------------------------------------------------------------------------------------------------------------------
 
 #define KVQ_INF_SLOT_FULL   (-7)         // the output would not fit the chunk's slot: nothing written past it

@@ -1,6 +1,7 @@
 // kvarq_amd/csrc/kvq_runtime.hip -- host runtime of libkvarq_hip.so: config and
 // error state, the target table, the scan object (batches -> kernels -> hits),
-// results.  The file reader / engine.findseqs driver lives in kvq_findseqs.hip.
+// results.  The engine.findseqs driver lives in kvq_findseqs.hip, its host reader in
+// kvq_reader.hip, its device routes in kvq_routes.hip.
 #include "kvq_host.h"
 
 #include <algorithm>
@@ -132,6 +133,17 @@ static void *pinned_take(size_t n, size_t *cap)
     return p;
 }
 static void pinned_give(void *p, size_t cap) { if (p && !(cache_on() && g_pin_blocks.put(p, cap))) (void)hipHostFree(p); }
+// a grow-only pinned buffer kept from call to call (the device routes' and the BAM runs'): contents are NOT preserved
+static int pinned_grow(void **p, size_t *cap, size_t need)
+{
+    if (*cap >= need) return KVQ_OK;
+    if (*p) (void)hipHostFree(*p);
+    *p = nullptr; *cap = 0;
+    const size_t want = need + need / 4;
+    if (hipHostMalloc(p, want, hipHostMallocDefault) != hipSuccess) { *p = nullptr; kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for scanning"); return KVQ_ERR_MEMORY; }
+    *cap = want;
+    return KVQ_OK;
+}
 
 int TablePool::reserve(size_t bytes, hipStream_t stream)
 {

@@ -96,7 +96,9 @@ def test_header_host_needs_the_whole_header_and_refuses_a_bad_one():
     assert L.kvq_bam_header_host(h, len(h), C.byref(nr)) == len(h) and nr.value == 50
     assert L.kvq_bam_header_host(h, len(h) - 1, C.byref(nr)) == -2
     assert L.kvq_bam_header_host(b'BAM\x02' + h[4:], len(h), C.byref(nr)) == -1
-    assert L.kvq_bam_header_host(h[:8] + struct.pack('<i', -1), 12 + len(h), C.byref(nr)) in (-1, -2)
+    l_text, = struct.unpack_from('<i', h, 4)
+    bad = h[:8 + l_text] + struct.pack('<i', -1) + h[12 + l_text:]          # n_ref = -1, every byte that is passed at hand
+    assert L.kvq_bam_header_host(bad, len(bad), C.byref(nr)) in (-1, -2)
 
 
 def _broken(field):

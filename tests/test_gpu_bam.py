@@ -290,3 +290,17 @@ def test_analyser_extract_hits_stop_and_rescan(tmp_path, monkeypatch):
     monkeypatch.delenv('KVQ_RECORD_CAP')
     two = engine.findseqs(q, seqs, records=True)
     _same(one, two)
+
+
+def test_file_that_hands_over_nothing_between_files_of_several_runs(tmp_path, monkeypatch):
+    """a header-only BAM hands no batch to the scan: the batch in flight keeps its text buffer"""
+    monkeypatch.setenv('KVQ_INFLATE_BATCH_MB', '2')
+    g = synth.genome()
+    seqs = synth.both_strands(synth.table(g))
+    cfg = dict(cases.PRODUCT, nthreads=4)
+    a, aq = _make(tmp_path, 'a', W.header(0), W.from_fastq(synth.reads(g, 50000, 20000, 150).tobytes()), block=30011)
+    b, bq = _make(tmp_path, 'b', W.header(0), W.from_fastq(synth.reads(g, 300000, 20000, 150).tobytes()), block=30011)
+    e, eq = _make(tmp_path, 'e', W.header(5), [])
+    for bams, fqs in (([a, e, b], [aq, eq, bq]), ([e, a, e], [eq, aq, eq])):
+        _three_way(bams, fqs, seqs, cfg)
+        assert engine.last_bam_report()['runs'] > 2

@@ -279,3 +279,56 @@ def test_run_that_reads_past_its_margin_is_repeated_with_its_window(tmp_path, mo
         rep = engine.last_inflate_report()
         assert rep['input_retries'] >= 1 and rep['runs'] >= 3, rep
 
+
+
+def test_file_that_hands_over_nothing_on_the_gzip_route(tmp_path, monkeypatch):
+    """an empty file, BGZF or plain gzip, between or around files of several batches: it hands no batch to the scan, and the
+    batch in flight keeps its text buffer (test_gpu_inflate pins the same for the block route)"""
+    monkeypatch.setenv('KVQ_INFLATE_BATCH_MB', '2')
+    monkeypatch.setenv('KVQ_GZIP_CHUNK_KB', '32')
+    t1, t2 = cases.multichunk(), cases.ragged(9, 3000, cases.RAGGED_TARGETS)
+    pa, pb = _write(tmp_path, 'pa.fastq.gz', gzip.compress(t1, 6)), _write(tmp_path, 'pb.fastq.gz', gzip.compress(t2, 6))
+    ba, bb = _write(tmp_path, 'ba.fastq.gz', bgzf(t1)), _write(tmp_path, 'bb.fastq.gz', bgzf(t2, level=1))
+    pe, be = _write(tmp_path, 'pe.fastq.gz', gzip.compress(b'')), _write(tmp_path, 'be.fastq.gz', bgzf(b''))
+    engine.config(**cases.PRODUCT)
+    for files in ([pa, be, bb], [ba, pe, pb], [pe, pa, be]):
+        host, dev = _both(files, cases.MULTI_SEQS)             # (asserts the route: a list with a plain gzip file takes the gzip route)
+        assert dev[0] == 'ok' and dev == host
+
+
+def _grow_case(tmp):
+    """test_text_buffer_grows_while_a_chunk_is_carried in a process whose text buffers are still as the call makes them"""
+    import pathlib
+    g = synth.genome()
+    seqs = synth.both_strands(synth.table(g))
+    reads = synth.reads(g, 0, 10000, 150).tobytes()              # 3.25 MB: more than one run compressed
+    one = cases.rec('rep', 'ACGT' * 37 + 'AC', 'I' * 150)
+    text = reads + one * (8_000_000 // len(one))
+    z = gzip.compress(text, 6)
+    assert 512 << 10 < len(gzip.compress(reads, 6)) and len(z) < 1024 << 10 and len(text) < 16_000_000
+    p = _write(pathlib.Path(tmp), 'grow.fastq.gz', z)
+    engine.config(**dict(cases.PRODUCT, nthreads=4))
+    dev, d_route = _run([p], seqs, 'device_any')                  # (first: no call before it has made the buffers larger)
+    rep = engine.last_inflate_report()
+    host, h_route = _run([p], seqs, 'host')
+    assert (h_route, d_route) == ('host', 'device_gzip')
+    assert dev[0] == 'ok' and dev == host and len(dev[1]) > 20
+    # Two runs: the first ends inside the reads, in the middle of a chunk, and the second holds the rest of the file.  A buffer
+    # starts with room for a batch, a chunk and 64 bytes, a quarter more and 256 (DevBuf::ensure): the larger run does not fit
+    assert rep['runs'] - rep['input_retries'] == 2
+    assert len(text) / 2 > ((2 << 20) + (1 << 20) + 64) * 1.25 + 256
+    print('grow case ok')
+
+
+def test_text_buffer_grows_while_a_chunk_is_carried(tmp_path):
+    """the second run of the file inflates to more than the text buffer holds (one record repeated: 8 MB out of 50 KB) while
+    the unfinished chunk of the first run sits at the buffer's front: the buffer grows and the chunk moves along.  The buffers
+    are kept from call to call and only grow, so the case runs in a fresh process, as its first call."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, KVQ_INFLATE_BATCH_MB='2', KVQ_GZIP_CHUNK_KB='32')      # text buffers of 3 MiB and a bit, runs of 512 KiB compressed
+    code = 'import sys; sys.path[:0] = [%r, %r]; import test_gpu_gzip_spec as T; T._grow_case(%r)' % (os.path.dirname(here), here, str(tmp_path))
+    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and 'grow case ok' in r.stdout, r.stdout + r.stderr

@@ -3,7 +3,7 @@ CPU checks of plain-gzip inflate by speculative chunk decoding (DESIGN section 1
 kvq_inflate_gzip_host: the decoder source of kvq_inflate.h and the chunked algorithm of
 kernels_gzip.hip that the GPU runs -- block finder, speculative decode with markers, chain check
 with refutations and re-decodes, window resolution, marker replacement -- against zlib under the
-host reader's rules (GzSerial in kvq_findseqs.hip): members crossed when more than 10 bytes follow
+host reader's rules (GzSerial in kvq_reader.hip): members crossed when more than 10 bytes follow
 a final block, the next header searched within 10 bytes, a file cut short ends the text, no CRC32.
 """
 import gzip
