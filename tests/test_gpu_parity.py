@@ -801,11 +801,16 @@ def test_long_records_with_ragged_quality_go_through_the_redo_exactly():
     """a dozen records of 1.1 .. 9 kB that outgrow their tiles' look-ahead, their score lines full of dips, ties between
     equally long good runs and runs that cross the 16-byte, 1 KiB and 4 KiB seams of the wave-parallel trim: hits, read
     lengths and counters equal the oracle's (the redo of skipped tiles: kvq_collect_skipped, kvq_trim_records'
-    long-line path, the matcher's launch for long reads)"""
+    long-line path, the matcher's launch for long reads).  Each long record holds a 40-base sequence of the table inside
+    the run its trim must pick, so its hit reveals that trim: file_pos and readlength as tests/trim_matrix.py's plain
+    statement of the trim gives them"""
     import random
+    import trim_matrix as TM
     rng = random.Random(20261004)
+    rng_probe = random.Random(20261018)                            # (a stream of its own: the score lines stay what they were)
     g = synth.genome()
-    seqs = synth.both_strands(synth.table(g))
+    seqs = synth.both_strands(synth.table(g) + [TM.probe()])
+    revealed = []
     n, L = 120000, 150
     rb = synth.record_bytes(L)
     plain = synth.reads(g, 0, n, L)
@@ -833,12 +838,19 @@ def test_long_records_with_ragged_quality_go_through_the_redo_exactly():
             q[:] = bytes(rng.choice(b'#I') for _ in range(ln))
             a = 1024 * (1 + rng.randrange(max(1, ln // 1024 - 1))) - 37
             q[a:a + 90] = b'I' * 90; q[a - 1:a] = b'#'; q[a + 90:a + 91] = b'#'
+        start, rl = TM.trim(bytes(q), ord('.'))
+        assert rl >= 64
+        p = start + rng_probe.randrange(0, rl - TM.PROBE_LEN + 1)
+        bases = bases[:p] + TM.probe() + bases[p + TM.PROBE_LEN:]
         pieces.append(plain[at:cut].tobytes()); at = cut
-        pieces.append(b'@long%d 1:N:0\n' % i + bases + b'\n+\n' + bytes(q) + b'\n')
+        head = b'@long%d 1:N:0\n' % i
+        pieces.append(head + bases + b'\n+\n' + bytes(q) + b'\n')
+        revealed.append((sum(len(x) for x in pieces[:-1]) + len(head) + start, rl))
     pieces.append(plain[at:].tobytes())
     text = np.frombuffer(b''.join(pieces), dtype=np.uint8)
     cfg = dict(cases.PRODUCT)
     o = O.scan_memory(text, seqs, fold=True, **dict(cfg, nthreads=16))
+    assert set(revealed) <= set((h.file_pos, h.readlength) for h in o['hits'])
     t = scan.Table(seqs, **cfg)
     s = scan.Scanner(t)
     d = scan.DeviceBuffer(text.nbytes); d.upload(text)
@@ -852,6 +864,9 @@ def test_long_records_with_ragged_quality_go_through_the_redo_exactly():
         assert r['coverage'].tolist() == o['coverage'] and r['mutations'].tolist() == o['mutations']
         assert r['stats']['records_parsed'] == n + len(lens) and r['stats']['readlengths'] == o['stats']['readlengths']
         assert r['stats']['nseqhits'] == o['stats']['nseqhits'] and r['stats']['nseqbasehits'] == o['stats']['nseqbasehits']
+        # every long record is revealed: the hit of its probe carries its trim
+        got = set((h.file_pos, h.readlength) for h in r['hits'])
+        assert len(revealed) == len(lens) and all(x in got for x in revealed), [x for x in revealed if x not in got]
     d.free(); s.close(); t.close()
 
 
