@@ -130,7 +130,7 @@ kvq_index_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__
 struct KvqSkippedTile { uint32_t a, b, own_begin, own_end, seen, first; };
 
 // How many items a kernel has to deal with, when that number is only known on the device (the redo of skipped tiles is
-// enqueued behind every seed-filter launch, without the host looking: kvq_runtime.hip): `n` when d_n is null, else
+// enqueued behind every seed-filter launch, without the host looking: kvq_scan.hip): `n` when d_n is null, else
 // *d_n >> shift -- nothing when the batch's fail word says the whole batch is redone anyway (bit 0), and a number beyond
 // `cap` (the tables are full) raises that bit, so that the batch IS redone as a whole.  The kernels walk their items with a
 // stride of their grid: a launch of fixed size serves any count.

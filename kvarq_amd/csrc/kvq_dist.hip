@@ -343,14 +343,7 @@ extern "C" int32_t kvq_scan_gather_hits(kvq_scan *s, kvq_comm *c)
     if ((rc = c->bcast_flush(s->stream))) return rc;
     // to the host (behind the counters, as `finish` lays the landing buffer out); hitseq offsets: rank r's start at base[r]
     const size_t ctr_b = (size_t)(s->pin_res - s->pin);
-    if (ctr_b + L.total > s->pin_cap) {
-        const size_t want = (ctr_b + L.total) * 5 / 4 + (1 << 20);
-        uint8_t *np = nullptr;
-        if (hipHostMalloc((void **)&np, want, hipHostMallocDefault) != hipSuccess) { kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
-        memcpy(np, s->pin, ctr_b);
-        (void)hipHostFree(s->pin);
-        s->pin = np; s->pin_cap = want; s->pin_res = np + ctr_b;
-    }
+    if (ctr_b + L.total > s->pin_cap) { if ((rc = grow_landing(s, ctr_b + L.total, ctr_b))) return rc; s->pin_res = s->pin + ctr_b; }
     KVQ_HIP(hipMemcpyAsync(s->pin_res, dst, L.total, hipMemcpyDeviceToHost, s->stream));
     KVQ_HIP(hipStreamSynchronize(s->stream));
     long long *off = reinterpret_cast<long long *>(s->pin_res + L.hitseq_off);

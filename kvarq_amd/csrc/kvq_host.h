@@ -57,6 +57,9 @@ struct kvq_table {
     struct SeedIndex *index = nullptr;   // kernels_seeded
     int64_t ctr_len, off_nseqhits, off_nseqbasehits, off_cov, off_mut;
 };
+static inline size_t kvq_align256(size_t n) { return (n + 255) & ~(size_t)255; }
+// the counters' bytes in the landing buffer of finish (kvq_scan::pin): the result arrays start behind them
+static inline size_t kvq_ctr_bytes(const kvq_table *t) { return kvq_align256((size_t)t->ctr_len * 8); }
 
 // where each array of a finished scan lives inside the result buffer (device copy and pinned host copy alike)
 struct KvqResultLayout {
@@ -68,9 +71,6 @@ struct Batch {
     std::vector<int64_t> chunk_off;
     bool redone = false;      // its seed-filter pass failed validation; an exhaustive redo batch follows
     bool is_redo = false;     // this batch is such a redo (or the redo of another batch's skipped tiles)
-    bool skips_done = false;  // its skipped tiles have been scanned again
-    size_t skip_at = 0;       // its list of skipped tiles in the table pool
-    uint32_t tile_bytes = 0;  // bytes a tile owned when it was scanned
     const uint8_t *staged = nullptr;   // device text owned by the caller while the batch is in flight (kvq_scan_staged): a host batch for every other purpose
 };
 
@@ -95,6 +95,39 @@ struct KvqRedo {                      // where the pieces lie inside kvq_scan::d
     static size_t bytes() { return 256 + (size_t)KVQ_REDO_CAP * (16 + 4 + 4 + 4); }
     __host__ __device__ explicit KvqRedo(void *p) { char *c = (char *)p; count = (unsigned int *)c; nl4 = (uint32_t *)(c + 256); rec_start = nl4 + 4 * (size_t)KVQ_REDO_CAP; read_off = rec_start + KVQ_REDO_CAP; read_len = (int32_t *)(read_off + KVQ_REDO_CAP); }
 };
+
+// ---- where the pieces lie inside three small blocks of a scan -----------------
+#define KVQ_MAX_BATCHES 65536
+// kvq_scan::d_small (device): the eight small words kvq_publish_small hands to the host -- [0] arena_n u32, [8] blob_n, [16] err, [24] err of the batch
+// in flight (u64) --, a range word per batch and one more (hits of batch b = arena[range[b], range[b + 1])), a "speculation failed" word per batch,
+// the staging counters of the batch in flight (records, longest, read-length histogram)
+struct KvqSmall {
+    static constexpr size_t BLOB_N = 8, ERR = 16, ERR_STAGE = 24, RANGE = 64, FAIL = RANGE + 4 * (KVQ_MAX_BATCHES + 1),
+                            STAGE = (FAIL + 4 * KVQ_MAX_BATCHES + 255) & ~(size_t)255, BYTES = STAGE + 8 * KVQ_STAGE_SLOTS * KVQ_STAGE_COPIES;
+    static constexpr unsigned int PUBLISHED_WORDS = 8;
+    static constexpr size_t ERR_WORD = ERR / 8, ERR_STAGE_WORD = ERR_STAGE / 8;      // kvq_reset_state writes 8-byte words: zeros, but all ones ("no error") into these two
+    static_assert(ERR % 8 == 0 && ERR_STAGE % 8 == 0 && BYTES % 8 == 0 && ERR_STAGE + 8 <= RANGE, "kvq_reset_state writes 8-byte words");
+    unsigned int *arena_n, *range, *fail; unsigned long long *blob_n, *err, *err_stage, *stage_ctr;
+    explicit KvqSmall(void *p)
+    {
+        char *c = (char *)p; arena_n = (unsigned int *)c; range = (unsigned int *)(c + RANGE); fail = (unsigned int *)(c + FAIL);
+        blob_n = (unsigned long long *)(c + BLOB_N); err = (unsigned long long *)(c + ERR); err_stage = (unsigned long long *)(c + ERR_STAGE); stage_ctr = (unsigned long long *)(c + STAGE);
+    }
+};
+// kvq_scan::pin_small (pinned): the copy of the small words, the fail word of the host batch in flight (copied behind its kernels), and what
+// kvq_publish_small leaves at the end of a scan: the fail word of every batch, the KvqFinishState
+struct KvqPinSmall {
+    static constexpr size_t CUR_FAIL = 40, FAIL = 64, STATE = FAIL + 4 * (size_t)KVQ_MAX_BATCHES, STATE_BYTES = 512, BYTES = STATE + STATE_BYTES;
+    static_assert(4 * KvqSmall::PUBLISHED_WORDS <= CUR_FAIL && CUR_FAIL + 4 <= FAIL, "the pieces of pin_small overlap");
+    unsigned int *small, *cur_fail, *fail, *state;
+    explicit KvqPinSmall(uint8_t *p) { small = (unsigned int *)p; cur_fail = (unsigned int *)(p + CUR_FAIL); fail = (unsigned int *)(p + FAIL); state = (unsigned int *)(p + STATE); }
+};
+// kvq_scan::pin_rec (pinned), laid out for `hcap` hits: the record words, the offset and the length of every hit's record, the store
+struct KvqPinRec {
+    int64_t *off; int32_t *len; uint8_t *store;
+    static size_t bytes(uint64_t hcap, uint64_t scap) { return 256 + kvq_align256(hcap * 8) + kvq_align256(hcap * 4) + scap; }
+    KvqPinRec(uint8_t *p, uint64_t hcap) { off = (int64_t *)(p + 256); len = (int32_t *)(p + 256 + kvq_align256(hcap * 8)); store = (uint8_t *)len + kvq_align256(hcap * 4); }
+};
 int kvq_live_scans();                 // scan objects alive in this process
 // the persistent scan kernels of a process run one behind the other (two at once only get in each other's way): a launch waits for
 // the event the last one published, on its own stream, right in front of its scan kernel -- its table upload and kvq_expand_tiles do not wait
@@ -111,7 +144,7 @@ struct kvq_scan {
     hipStream_t stream = nullptr;
     bool force_exhaustive = false;
     // counters
-    unsigned long long *d_ctr = nullptr; bool own_ctr = false; DevBuf d_ctr_own;
+    unsigned long long *d_ctr = nullptr; DevBuf d_ctr_own;
     std::vector<int64_t> h_ctr;
     // per-batch scratch
     uint32_t cus = 0;                  // compute units of the scan's device (asked once)
@@ -120,12 +153,12 @@ struct kvq_scan {
     uint32_t surv_cap = 0;             // slots of d_surv's list (KVQ_SURV_CAP, or what the environment cut it to)
     DevBuf d_surv;                     // what passed the scan kernel's 16-base test, for kvq_verify_survivors (KvqSurvivors)
     DevBuf d_redo;                     // the redo of skipped tiles (KvqRedo: count, newline quadruples, record starts, trimmed reads)
-    DevBuf d_skipped, d_chunk_off, d_seg_base, d_seg_cnt, d_chunk_nrec, d_rec_base, d_nl4, d_rec_start, d_read_off, d_read_len;
+    DevBuf d_seg_base, d_seg_cnt, d_chunk_nrec, d_rec_base, d_nl4, d_rec_start, d_read_off, d_read_len;
     // hit arena
     DevBuf d_covdiff;                  // coverage marks (KvqParams::covdiff)
     uint32_t tile_bytes = 0;           // bytes a tile of the seed-filter kernel owns (0 = not chosen yet; kvq_choose_tile)
     uint32_t rec_bytes = 0;            // average record among the first bytes of the text (0 = unknown)
-    DevBuf d_arena, d_blob, d_small;   // d_small: arena_n, batch range words, blob_n, err
+    DevBuf d_arena, d_blob, d_small;   // d_small: KvqSmall; the seven pointers below are its pieces
     uint32_t arena_cap = 0; uint64_t blob_cap = 0;
     unsigned int *d_arena_n = nullptr, *d_range = nullptr, *d_fail = nullptr, *cur_fail = nullptr;
     unsigned long long *d_blob_n = nullptr, *d_err = nullptr, *d_err_stage = nullptr, *d_stage_ctr = nullptr;
@@ -149,7 +182,6 @@ struct kvq_scan {
     bool host_batches = false;
     int64_t host_pending = -1;           // index of the host batch in flight (kvq_scan_host_async), -1: none
     hipEvent_t ev_chain = nullptr;       // this scan's last seed-filter launch and its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles: what the next scan of the process waits for)
-    int64_t records = 0;
     int64_t parsed = 0, total = 0;
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_free;     // ev_free: pairs of earlier scans, reused
@@ -160,7 +192,7 @@ struct kvq_scan {
     uint8_t *pin_res = nullptr;                   // where the result arrays start inside pin (behind the counters)
     size_t spec_bytes = 1u << 20;                 // result bytes fetched together with the counters, before their number is known (the last scan's)
     uint8_t *pin = nullptr; size_t pin_cap = 0;   // pinned landing buffer of finish: the result arrays, then the counters
-    uint8_t *pin_small = nullptr; size_t pin_small_cap = 0;   // pinned landing buffer for the scan's small words and fail flags
+    uint8_t *pin_small = nullptr; size_t pin_small_cap = 0;   // pinned landing buffer for the scan's small words and fail flags (KvqPinSmall)
     KvqResultLayout res;                          // where the arrays sit inside pin
     uint64_t n_hits = 0;
     bool finished = false;
@@ -174,7 +206,7 @@ struct kvq_scan {
     DevBuf d_rkey, d_roff, d_rlen, d_rdir, d_rstore, d_rsmall, d_rres;
     uint32_t rslots = 0;                          // slots of the table (a power of two, >= 2 x arena_cap)
     unsigned long long rstore_cap = 0;            // bytes of the store (KVQ_RECORD_CAP caps the first one)
-    uint8_t *pin_rec = nullptr; size_t pin_rec_cap = 0;   // pinned: the record words, offsets [rec_hcap], lengths [rec_hcap], store bytes [rec_scap]
+    uint8_t *pin_rec = nullptr; size_t pin_rec_cap = 0;   // pinned (KvqPinRec): the record words, offsets [rec_hcap], lengths [rec_hcap], store bytes [rec_scap]
     uint64_t rec_hcap = 0, rec_scap = 0;
     uint64_t rec_tail_n = 0, rec_tail_b = 0;      // what the tail fetched ahead of time (offsets / lengths of that many hits, that many store bytes)
     uint64_t rec_spec_n = 4096, rec_spec_b = 1u << 20;   // ... guessed from the last scan of this handle
@@ -196,7 +228,7 @@ int32_t  kvq_scan_pick(int k, int stride, bool ix_dense, uint32_t rec_bytes, uin
 // synth.hip
 // (C ABI only)
 
-// kvq_runtime.hip: a batch whose text the CALLER has put into device memory and keeps there only until the next batch
+// kvq_scan.hip: a batch whose text the CALLER has put into device memory and keeps there only until the next batch
 // is handed over (the device-inflate route of findseqs): scanned, settled and -- on a hit-arena overflow -- fed again
 // like a host batch, never replayed from its buffer
 int kvq_scan_staged(kvq_scan *s, const uint8_t *d_text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t fpos_base);

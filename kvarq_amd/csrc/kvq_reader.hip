@@ -15,7 +15,45 @@
 #include <sys/mman.h>
 #include <unistd.h>
 
-int64_t kvq_tail_record(const uint8_t *buf, int64_t n);
+// ---------------------------------------------------------------------------
+// fastq_rewind / fastq_read chunk cuts on an in-memory stream
+// ---------------------------------------------------------------------------
+
+// length of the trailing partial record of buf[0..n): going backwards, the
+// first line start '@' met after a line start '+' (workhorse.c:696-718)
+int64_t kvq_tail_record(const uint8_t *buf, int64_t n)
+{
+    bool plus_seen = false;
+    for (int64_t k = n - 1; k >= 2; k--) {                 // i = n - k runs 1 .. n-2 (706)
+        const uint8_t prev = buf[k - 1];
+        if (prev != '\n' && prev != '\r') continue;
+        if (buf[k] == '+') plus_seen = true;
+        else if (buf[k] == '@' && plus_seen) return n - k;
+    }
+    return -1;
+}
+
+extern "C" int64_t kvq_chunk_offsets(const uint8_t *data, int64_t nbytes, int64_t *offsets, int64_t cap)
+{
+    int64_t n = 0, cs = 0, fill = 0;
+    for (;;) {
+        const int64_t want = KVQ_SCANBUFSIZE - (fill - cs);
+        const int64_t have = nbytes - fill;
+        if (have >= want) {                                // buffer filled, source not dry: cut (916-943)
+            const int64_t end = fill + want;
+            const int64_t keep = kvq_tail_record(data + cs, end - cs);
+            if (keep < 0) return -1;
+            if (n < cap) offsets[n] = cs;
+            n++;
+            cs = end - keep; fill = end;
+        } else {                                           // short read: eof, no cut (901-910)
+            if (nbytes > cs) { if (n < cap) offsets[n] = cs; n++; }
+            break;
+        }
+    }
+    if (n < cap + 1) offsets[n] = nbytes;
+    return n;
+}
 
 // ---------------------------------------------------------------------------
 // the inflated stream of a list of files

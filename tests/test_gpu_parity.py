@@ -951,28 +951,53 @@ def test_reads_with_more_work_items_than_a_queue_holds_are_dealt_with_in_turns()
     s.close(); t.close()
 
 
-def test_speculation_failure_falls_back_to_the_exact_split():
-    """a FastQ whose base lines may start with '@' or '+' defeats the text heuristic;
-    the validation pass must notice and the rescan must give the reference's answer"""
+def _quirk_text(quirky_from=0, every=False):
+    """4000 records of 60-230 bases, about 1 MB; from record `quirky_from` on, base lines may start with '@' or '+' and
+    the quality lines are drawn from '@+IIII' (the records before it are plain: all-'I' qualities).  every: from there
+    on EVERY quality line starts with '@' and every base line that does not start with '@' starts with '+' (same bytes
+    otherwise, same lengths)"""
     import random
     rng = random.Random(99)
     target = cases.QUIRK_SEQ
     recs = []
     for i in range(4000):
         bases = cases.randseq(rng, rng.randint(60, 200))
-        if i % 7 == 0:
+        if i % 7 == 0 and i >= quirky_from:
             bases = '@' + bases[1:]
-        if i % 11 == 0:
+        if i % 11 == 0 and i >= quirky_from:
             bases = '+' + bases[1:]
         if i % 5 == 0:
             at = rng.randint(1, len(bases) - 1)
             bases = (bases[:at] + target)[:230]
-        q = ''.join(rng.choice('@+IIII') for _ in bases)
+        q = ''.join(rng.choice('@+IIII') for _ in bases) if i >= quirky_from else 'I' * len(bases)
+        if every and i >= quirky_from:
+            q = '@' + q[1:]
+            if bases[0] != '@':
+                bases = '+' + bases[1:]
         recs.append(cases.rec('r%d' % i, bases, q))
-    data = np.frombuffer(b''.join(recs), dtype=np.uint8)
-    seqs = synth.both_strands([target.encode()])
-    cfg = dict(cases.PRODUCT, Amin='!')
-    o = O.scan_memory(data, seqs, fold=True, **dict(cfg, nthreads=4))
+    return recs
+
+
+QUIRK_CFG = dict(cases.PRODUCT, Amin='!')
+_quirk_memo = {}
+
+
+def _quirk_case(quirky_from=0, every=False):
+    """(records, text, sequences, the oracle's answer): computed once, shared, left unchanged"""
+    if (quirky_from, every) not in _quirk_memo:
+        recs = _quirk_text(quirky_from, every)
+        data = np.frombuffer(b''.join(recs), dtype=np.uint8)       # (over bytes: read-only)
+        assert not data.flags.writeable
+        seqs = synth.both_strands([cases.QUIRK_SEQ.encode()])
+        _quirk_memo[quirky_from, every] = (recs, data, seqs, O.scan_memory(data, seqs, fold=True, **dict(QUIRK_CFG, nthreads=4)))
+    return _quirk_memo[quirky_from, every]
+
+
+def test_speculation_failure_falls_back_to_the_exact_split():
+    """a FastQ whose base lines may start with '@' or '+' defeats the text heuristic;
+    the validation pass must notice and the rescan must give the reference's answer"""
+    _, data, seqs, o = _quirk_case()
+    cfg = QUIRK_CFG
     t = scan.Table(seqs, **cfg)
     s = scan.Scanner(t)
     s.scan_host(data)
@@ -982,6 +1007,104 @@ def test_speculation_failure_falls_back_to_the_exact_split():
     assert r['coverage'].tolist() == o['coverage']
     assert len(o['hits']) > 100
     s.close(); t.close()
+
+
+def _findseqs_path(fname, seqs, flags):
+    """kvq_scan_path of one kvq_findseqs_ex call (engine.findseqs keeps it to itself)"""
+    import ctypes as C
+    L = _lib.lib()
+    farr = (C.c_char_p * 1)(fname.encode())
+    bufs = [C.create_string_buffer(q, len(q) + 1) for q in seqs]
+    sarr = (C.c_char_p * len(seqs))(*[C.cast(q, C.c_char_p) for q in bufs])
+    lens = (C.c_int32 * len(seqs))(*[len(q) for q in seqs])
+    h = L.kvq_findseqs_ex(farr, 1, sarr, lens, len(seqs), flags)
+    try:
+        assert h and _lib.last_error()[0] == 0, _lib.last_error()
+        return L.kvq_scan_path(h)
+    finally:
+        L.kvq_findseqs_free(h)
+
+
+def _assert_redone_and_exact(r, o):
+    assert r['path']['rescanned'] is True, r['path']
+    assert r['stats']['records_parsed'] == 4000
+    assert tuple(r['hits']) == tuple(o['hits']) and r['hitseqs'] == o['hitseqs']
+    assert r['stats']['readlengths'] == o['stats']['readlengths']
+    assert r['coverage'].tolist() == o['coverage']
+
+
+@pytest.mark.parametrize('feed', ['host', 'device', 'findseqs', 'two_device_batches'])
+def test_a_failed_speculation_redoes_the_whole_batch_on_every_feed(feed, tmp_path):
+    """a text whose speculated record split fails validation, so that the batch is rolled back and scanned again as a
+    whole, exhaustively (path['rescanned']).  The text of test_speculation_failure_falls_back_to_the_exact_split does
+    not do that today: a tile takes as its first record the first of its first eight lines that starts with '@' and has
+    a line starting with '+' two lines on, and in that text a false such pair in front of the true one needs a tile
+    boundary inside the six bytes of a header line; the seed-filter pass gets through it without a single skipped
+    tile.  The variation used here is the smallest that makes it sure: the same records with the same lengths, but
+    EVERY quality line starts with '@' and every base line that does not start with '@' starts with '+' -- a tile
+    that begins in a header, base or '+' line (more than half of all bytes) then meets quality line / base line as
+    a false '@' ... '+' pair first.  That redo is reached from three places -- a host batch is redone when it is settled (scan_host), a device batch
+    when the scan is finished (scan_device), a batch staged by the device-inflate route of findseqs when the next one
+    is handed over or the scan ends (a BGZF file of the same text) -- and each must give the oracle's answer, every
+    record counted once.  'two_device_batches' is the one variation: the first 2000 records are plain (no '@' / '+'
+    at the start of a base line, all-'I' qualities), cut from the quirky rest at the record boundary, and the two
+    halves are handed over as two device batches.  Only the second is redone; its redo's hits lie in a range of
+    their own behind both batches, and the result must equal one scan of the whole text (and the oracle's)."""
+    recs, data, seqs, o = _quirk_case(2000 if feed == 'two_device_batches' else 0, every=True)
+    assert len(o['hits']) > 100
+    if feed == 'findseqs':
+        from test_host_logic import bgzf
+        p = str(tmp_path / 'quirk.fastq.gz')
+        with open(p, 'wb') as f:
+            f.write(bgzf(data.tobytes()))
+        before = engine.get_config()
+        try:
+            engine.config(**QUIRK_CFG)
+            r = engine.findseqs(p, seqs, inflate='device')
+            assert engine.last_inflate() == 'device'
+            of = O.findseqs(p, seqs, **dict(QUIRK_CFG, nthreads=4))
+            path = _findseqs_path(p, seqs, engine.INFLATE_FLAGS['device'])      # (the result has no path: the same call through the C ABI)
+        finally:
+            engine.config(**before)
+        assert path & engine.PATH_DEVICE_INFLATE and path & 4, hex(path)          # staged text, and a whole batch redone
+        assert tuple(r['hits']) == tuple(of['hits']) == tuple(o['hits'])
+        assert [bytes(h) for h in r['hitseqs']] == of['hitseqs']
+        assert r['stats'] == of['stats'] and r['stats']['records_parsed'] == 4000
+        return
+    t = scan.Table(seqs, **QUIRK_CFG)
+    s = scan.Scanner(t)
+    bufs = []
+    try:
+        if feed == 'host':
+            s.scan_host(data)
+            r = s.finish()
+        else:
+            d = scan.DeviceBuffer(data.nbytes); bufs.append(d); d.upload(data)
+            if feed == 'device':
+                s.scan_device(d.ptr, data.nbytes, scan.chunk_offsets(data))
+                r = s.finish()
+            else:
+                cut = sum(len(x) for x in recs[:2000])
+                a, b = data[:cut], data[cut:]
+                co_a, co_b = scan.chunk_offsets(a), scan.chunk_offsets(b)
+                s.scan_device(d.ptr, data.nbytes, np.concatenate([co_a, co_b[1:] + cut]))
+                whole = s.finish()
+                assert whole['path']['rescanned'] is True, whole['path']
+                s.reset()
+                da = scan.DeviceBuffer(a.nbytes); bufs.append(da); da.upload(a)
+                db = scan.DeviceBuffer(b.nbytes); bufs.append(db); db.upload(b)
+                s.scan_device(da.ptr, a.nbytes, co_a)
+                s.scan_device(db.ptr, b.nbytes, co_b, fpos_base=cut)
+                r = s.finish()
+                assert tuple(r['hits']) == tuple(whole['hits']) and r['hitseqs'] == whole['hitseqs']
+                assert (r['counters'] == whole['counters']).all()
+                assert sum(1 for h in r['hits'] if h[1] < cut) > 50 and sum(1 for h in r['hits'] if h[1] >= cut) > 50
+        _assert_redone_and_exact(r, o)
+    finally:
+        s.close()
+        for d in bufs:
+            d.free()
+        t.close()
 
 
 def test_dense_table_overflows_the_candidate_queues_gracefully():
