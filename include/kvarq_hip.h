@@ -193,11 +193,54 @@ const int64_t *kvq_scan_hit_record_off(const kvq_scan *s);
 const int32_t *kvq_scan_hit_record_len(const kvq_scan *s);
 int64_t        kvq_scan_record_bytes(const kvq_scan *s);
 
+/* ---- the profile of the input (the reference's `kvarq show -Q q -i`, kvarq/cli.py:201-221, and the guesses of Fastq.__init__ --
+ * there from samples of the file, here exact, from every record while its text is in device memory) ----
+ * The profile covers exactly the records the scan counts in records_parsed: the complete four-newline records of every chunk
+ * (a partial tail of a chunk is dropped, as the scan drops it).  For a record with newlines n0..n3 its BASES LINE is the
+ * bytes strictly between n0 and n1, its SCORE LINE the bytes strictly between n2 and n3; bytes are raw (a '\r' is a byte
+ * of its line).  One flat int64 array of kvq_profile_len(ncut) = 8 + 256 + 256 + 1025 + ncut * 1025 words:
+ *   [0] records                      [1] bytes on bases lines          [2] bytes on score lines
+ *   [3] records whose score line and bases line differ in length
+ *   [4] longest bases line + 1 (0 = none; a maximum, not a sum)        [5..7] reserved, 0
+ *   [8 .. +256)     score_bytes[b]: occurrences of byte value b on score lines
+ *   [264 .. +256)   base_bytes[b]: the same for bases lines
+ *   [520 .. +1025)  raw_lengths[min(L, 1024)] over the bases-line lengths L
+ *   [1545 + 1025 k .. +1025), one block per cutoff k: longest_k + 1 (a maximum), then trimmed_k[0 .. 1023]
+ * trimmed_k / longest_k: the engine's own quality trim at Amin = cutoffs[k] (workhorse.c:1055-1068, as kvq_trim_records
+ * applies it: the longest run of score bytes >= Amin compared as signed char, the line's closing newline a byte like
+ * the others -- it ends the last run when it is below Amin --, the first of equally long runs), counted like add_rl
+ * (workhorse.c:394-402): before the length gate, lengths of 1024 and more in no bin but in longest_k.  So trimmed_k is, word
+ * for word, the readlengths / KVQ_CTR_LONGEST part of the counters of a scan configured with Amin = cutoffs[k], whatever its
+ * other settings.  (Not Fastq.cutoff, whose run at the end of a line does not count: the profile tells what the SCAN will do.)
+ * 0 <= ncut <= KVQ_PROFILE_MAX_CUTOFFS; any byte value, duplicates included.
+ *   [0] == sum(raw_lengths) == sum(trimmed_k) + (reads of 1024 and more at k) == counters[KVQ_CTR_RECORDS],
+ *   sum(score_bytes) == [2], sum(base_bytes) == [1].
+ * kvq_scan_set_profile: ncut >= 0 turns the profile on with these cutoffs, ncut < 0 off; before the first batch or after
+ * kvq_scan_reset (KVQ_ERR_RUNTIME otherwise), and not with a communicator (the maxima would need a reduction of their own:
+ * KVQ_ERR_RUNTIME, from this call or from kvq_scan_set_comm).  Every batch is then profiled once, whatever route brought it and
+ * whatever the scan had to redo; kvq_scan_finish brings the array to the host.  kvq_scan_profile: the array (valid after
+ * kvq_scan_finish until the next reset), NULL when the profile is off; kvq_scan_profile_cutoffs: writes the cutoffs (up to 8
+ * bytes) and returns their number, -1 when off.  With the profile off nothing is enqueued or allocated for it. */
+#define KVQ_PROFILE_MAX_CUTOFFS 8
+enum { KVQ_PROF_RECORDS = 0, KVQ_PROF_BASE_LINE_BYTES = 1, KVQ_PROF_SCORE_LINE_BYTES = 2, KVQ_PROF_MISMATCHED = 3, KVQ_PROF_LONGEST = 4,
+       KVQ_PROF_SCORE_BYTES = 8, KVQ_PROF_BASE_BYTES = 264, KVQ_PROF_RAW_LENGTHS = 520, KVQ_PROF_RAW_BINS = 1025,
+       KVQ_PROF_CUTOFFS = 1545, KVQ_PROF_CUT_WORDS = 1025 };
+int64_t        kvq_profile_len(int32_t ncut);
+int32_t        kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int32_t ncut);
+const int64_t *kvq_scan_profile(const kvq_scan *s);
+int32_t        kvq_scan_profile_cutoffs(const kvq_scan *s, uint8_t *cutoffs8);
+/* host only, plain C++: the CPU twin of the profile kernel over the same definition -- test infrastructure and the
+ * definition in running code, not a fallback.  text[0, nbytes) with chunk_off[0..nchunks] as for kvq_scan_host; ADDS into
+ * out[0, kvq_profile_len(ncut)) (the maxima as maxima).  KVQ_OK, or KVQ_ERR_RUNTIME for bad arguments. */
+int32_t        kvq_profile_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                const uint8_t *cutoffs, int32_t ncut, int64_t *out);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
 double  kvq_scan_kernel_ms(const kvq_scan *s);
 double  kvq_scan_main_kernel_ms(const kvq_scan *s);
+double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_profile_records alone (0 when the profile is off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 int64_t kvq_scan_main_kernel_launches(const kvq_scan *s);
@@ -305,6 +348,18 @@ kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
 #define KVQ_FIND_RECORDS 4u
 kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
                           const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags);
+
+/* the same with the options as a structure (size: sizeof(kvq_find_opts), for later growth; flags: the KVQ_FIND_* above).
+ * KVQ_FIND_PROFILE: the scan profiles its input at cutoffs[0, n_cutoffs) (kvq_scan_set_profile; kvq_scan_profile after the
+ * call).  An empty sequence list is legal and gives a profile-only call.  opts == NULL: kvq_findseqs. */
+#define KVQ_FIND_PROFILE 8u
+typedef struct kvq_find_opts {
+    uint32_t size, flags;
+    int32_t  n_cutoffs;
+    uint8_t  cutoffs[8];
+} kvq_find_opts;
+kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
+                            const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts);
 
 /* destroys a scan returned by kvq_findseqs together with the table it built */
 void kvq_findseqs_free(kvq_scan *s);

@@ -12,6 +12,7 @@ OK, ERR_FORMAT, ERR_IO, ERR_MEMORY, ERR_RUNTIME, ERR_TYPE, ERR_DEVICE, ERR_RESCA
 CTR_RECORDS, CTR_LONGEST, CTR_HITS, CTR_READLENGTHS = 0, 1, 2, 4
 CELL_DENSE, CELL_DIAG, CELL_STAMPS = 0x1000, 0x2000, 0x4000      # kvq_scan_kernel_pick / kvq_scan_kernel
 FIND_RECORDS = 4                                                 # kvq_findseqs_ex: keep the records of the hits
+FIND_PROFILE = 8                                                 # kvq_findseqs_opts: profile the input
 
 
 class Config(C.Structure):
@@ -23,6 +24,10 @@ class LiveStats(C.Structure):
     _fields_ = [('records_parsed', C.c_int64), ('parsed', C.c_int64), ('total', C.c_int64),
                 ('rls_longest', C.c_int64), ('nseq', C.c_int32), ('running', C.c_int32),
                 ('sigints', C.c_int32), ('stop_requested', C.c_int32)]
+
+
+class FindOpts(C.Structure):
+    _fields_ = [('size', C.c_uint32), ('flags', C.c_uint32), ('n_cutoffs', C.c_int32), ('cutoffs', C.c_uint8 * 8)]
 
 
 class GzipReport(C.Structure):
@@ -91,8 +96,14 @@ PROTOTYPES = {
     'kvq_scan_hit_record_off': (P(i64), [vp]),
     'kvq_scan_hit_record_len': (P(i32), [vp]),
     'kvq_scan_record_bytes': (i64, [vp]),
+    'kvq_profile_len': (i64, [i32]),
+    'kvq_scan_set_profile': (i32, [vp, vp, i32]),
+    'kvq_scan_profile': (P(i64), [vp]),
+    'kvq_scan_profile_cutoffs': (i32, [vp, vp]),
+    'kvq_profile_host': (i32, [vp, i64, P(i64), i64, vp, i32, P(i64)]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
+    'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_gap_ms': (C.c_double, [vp, vp]),
     'kvq_scan_main_kernel_launches': (i64, [vp]),
     'kvq_scan_reset': (i32, [vp]),
@@ -115,6 +126,7 @@ PROTOTYPES = {
     'kvq_result_layout_words': (None, [C.c_uint64, C.c_uint64, vp]),
     'kvq_findseqs': (vp, [P(cp), i32, P(cp), P(i32), i32]),
     'kvq_findseqs_ex': (vp, [P(cp), i32, P(cp), P(i32), i32, C.c_uint32]),
+    'kvq_findseqs_opts': (vp, [P(cp), i32, P(cp), P(i32), i32, P(FindOpts)]),
     'kvq_findseqs_free': (None, [vp]),
     'kvq_host_chunk_plan': (i64, [P(cp), i32, P(i64), P(i64), i64, P(i64), P(i64), i64]),
     'kvq_poll_stats': (None, [P(LiveStats), P(i64), P(i64), P(i64), i32]),

@@ -45,6 +45,7 @@ class Analyser(object):
         self.coverages = None                   # OrderedDict name -> Coverage
         self.hits = self.hitseqs = self.stats = self.config = None
         self.records = None                     # the FastQ record of every hit, when ``scan`` kept them (records=True)
+        self.profile = None                     # the profile of the input, when ``scan`` took one (profile=<cutoffs>)
         self.results = {}                       # testsuite interpretation is out of scope: stays empty
         self.scantime = -1
 
@@ -63,11 +64,12 @@ class Analyser(object):
 
     # -- scanning ------------------------------------------------------------------
 
-    def scan(self, fastq, templates, do_reverse=True, records=False):
+    def scan(self, fastq, templates, do_reverse=True, records=False, profile=None):
         """``fastq``: a :class:`kvarq_amd.fastq.Fastq`; ``templates``: ordered mapping name -> plus-strand
         template (``Sequence``, text, or ``(text, left, right)``).  May raise ``FastqFileFormatException``.
         ``records=True`` keeps the FastQ record of every hit, gathered on the GPU during the scan, for
-        :meth:`extract_hits`."""
+        :meth:`extract_hits`.  ``profile=<cutoffs>`` keeps the ``kvarq_amd.profile.Profile`` of the input in
+        ``self.profile`` (``encode`` then adds ``info['profile']``)."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
         self.fastq_sizes = fastq.filesizes()
@@ -79,10 +81,11 @@ class Analyser(object):
         if do_reverse:
             seqs += [c.minus_seq.bases for c in self.coverages.values()]
         t0 = time.time()
-        ret = engine.findseqs(self.fastq_filenames, seqs, records=records)
+        ret = engine.findseqs(self.fastq_filenames, seqs, records=records, profile=profile)
         lo.debug('found %d hits' % len(ret['hits']))
         self.stats, self.hits, self.hitseqs = ret['stats'], ret['hits'], ret['hitseqs']
         self.records = ret.get('records')
+        self.profile = ret.get('profile')
         self.scantime = time.time() - t0
         self.update_coverages()
 
@@ -124,6 +127,7 @@ class Analyser(object):
             more['hits'] = [list(h) for h in self.hits]
             more['hitseqs'] = [h.decode('latin-1') if isinstance(h, bytes) else h for h in self.hitseqs]
         config = dict((k, v.decode('latin-1') if isinstance(v, bytes) else v) for k, v in self.config.items())
+        more_info = {'profile': self.profile.as_dict()} if self.profile is not None else {}
         return dict(
             analyses=self.results,
             info={
@@ -138,6 +142,7 @@ class Analyser(object):
                 'config': config,
                 'spacing': self.spacing,
                 'testsuites': {},
+                **more_info
             },
             stats=self.stats,
             coverages=[(name, c.serialize()) for name, c in self.coverages.items()],

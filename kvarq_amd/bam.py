@@ -198,6 +198,12 @@ class Bam(object):
     def Q2A(self, Q):
         return ASCII[Q + self.dQ]
 
+    def profile(self, cutoffs=None):
+        """a ``kvarq_amd.profile.Profile`` of the file's virtual FastQ text, taken on the GPU; cutoffs None: the
+        configured Amin"""
+        from . import profile as profile_
+        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs)
+
     def readrecordat(self, hit):
         raise IOError('the records of a BAM file are kept by the scan only: use Analyser.scan(..., records=True) '
                       'before extract_hits')

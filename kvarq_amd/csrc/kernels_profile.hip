@@ -1,0 +1,214 @@
+// kvarq_amd/csrc/kernels_profile.hip -- the profile of a batch (include/kvarq_hip.h): what bytes the score
+// and bases lines of its records hold, how long the bases lines are, and what the quality trim leaves of every record at
+// up to eight cutoffs.  One kernel over the record index of the exhaustive path (kvq_index_records); it reads the text
+// only inside its records and writes nothing but the profile array.
+#include "kvq_device.h"
+#include "../../include/kvarq_hip.h"
+
+// the cutoffs, a byte each (compared as signed char, like Amin)
+struct KvqProfileCuts { int32_t n; unsigned long long packed; };
+__device__ __forceinline__ int prof_amin(const KvqProfileCuts &C, int k) { return (int)(int8_t)(C.packed >> (8 * k)); }
+
+// where the pieces lie inside a workgroup's LDS (32-bit bins: a batch is < 4 GiB); `spread`: KVQ_PROF_COPIES copies of the two
+// byte histograms behind them, a lane adding to the copy of its number
+#define KVQ_PROF_COPIES 8
+struct KvqProfLds {
+    static constexpr uint32_t SCORE = 0, BASE = 256, RAW = 512, TRIM = RAW + KVQ_PROF_RAW_BINS, SCALARS = 16;
+    // scalars behind the last trimmed histogram: records, mismatched, longest raw line + 1, longest trimmed read + 1 per cutoff
+    static constexpr uint32_t S_RECORDS = 0, S_MISMATCH = 1, S_LONGEST = 2, S_CUT_LONGEST = 3;
+    __host__ __device__ static uint32_t scalars(int ncut) { return TRIM + (uint32_t)ncut * KVQ_RL_BINS; }
+    __host__ __device__ static uint32_t copies(int ncut) { return scalars(ncut) + SCALARS; }
+    __host__ __device__ static uint32_t words(int ncut, bool spread) { return copies(ncut) + (spread ? 2u * 256u * KVQ_PROF_COPIES : 0u); }
+};
+
+// one byte of every lane (where `valid`) into a 256-bin histogram in LDS.  Score and bases lines hold few distinct bytes,
+// and 64 lanes adding to one LDS word queue up: either the wave counts its equal bytes first (the first lane's byte, the
+// ballot of the lanes that hold the same one, ONE add of their number, until none is left), or the lanes spread their
+// adds over KVQ_PROF_COPIES copies of the histogram
+__device__ __forceinline__ void prof_byte(unsigned int *bins, unsigned int *copies, bool spread, uint32_t byte, bool valid, int lane)
+{
+    if (spread) {
+        if (valid) atomicAdd(&copies[byte * KVQ_PROF_COPIES + ((uint32_t)lane & (KVQ_PROF_COPIES - 1u))], 1u);
+        return;
+    }
+    unsigned long long todo = __ballot(valid);
+    while (todo) {                                   // (the same for every lane)
+        const int l = __ffsll((long long)todo) - 1;
+        const uint32_t v = (uint32_t)__shfl((int)byte, l, 64);
+        const unsigned long long same = __ballot(valid && byte == v);
+        if (lane == l) atomicAdd(&bins[v], (unsigned int)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+// the sixteen bytes [q, q + 16) of a line of `len` bytes whose newline lies at line[len]: one vector where it fits into the
+// line and its newline, bytes where the line ends inside it (never a byte behind the newline)
+__device__ __forceinline__ void prof_load16(const uint8_t *line, uint32_t len, uint32_t q, uint32_t w[4])
+{
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    if (q + 16u <= len + 1u) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) __builtin_memcpy(&w[d], line + q + 4u * d, 4);
+    } else if (q < len) {
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; j++) if (q + j < len) w[j >> 2] |= (uint32_t)line[q + j] << (8u * (j & 3u));
+    }
+}
+
+// a line of 1024 bytes or more (a long read from BAM): a KiB a step, sixteen bytes a lane
+__device__ void prof_long_bytes(const uint8_t *line, uint32_t len, unsigned int *bins, unsigned int *copies, bool spread, int lane)
+{
+    for (uint32_t o = 0; o < len; o += 1024u) {
+        const uint32_t q = o + 16u * (uint32_t)lane;
+        uint32_t w[4];
+        prof_load16(line, len, q, w);
+        const uint32_t n = q < len ? (len - q < 16u ? len - q : 16u) : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; j++) prof_byte(bins, copies, spread, (w[j >> 2] >> (8u * (j & 3u))) & 0xFFu, j < n, lane);
+    }
+}
+
+// one behind the last byte of line[0, len) that is below amin; 0: there is none (the answer in every lane)
+__device__ uint32_t prof_last_low(const uint8_t *line, uint32_t len, int amin, int lane)
+{
+    uint32_t last = 0;
+    for (uint32_t o = 0; o < len; o += 1024u) {
+        const uint32_t q = o + 16u * (uint32_t)lane;
+        uint32_t w[4];
+        prof_load16(line, len, q, w);
+        const uint32_t n = q < len ? (len - q < 16u ? len - q : 16u) : 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; j++)
+            if (j < n && (int)(int8_t)(w[j >> 2] >> (8u * (j & 3u))) < amin) last = q + j + 1u;
+    }
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)last, d, 64); last = o > last ? o : last; }
+    return last;
+}
+
+// a line of fewer than 64 NG - 1 bytes and its newline (qlen bytes with it): lane l holds bytes l, l + 64, ...
+template <int NG>
+__device__ __forceinline__ void prof_short_load(const uint8_t *line, uint32_t qlen, int lane, uint8_t by[NG])
+{
+#pragma unroll
+    for (int k = 0; k < NG; k++) {
+        const uint32_t i = 64u * (uint32_t)k + (uint32_t)lane;
+        by[k] = line[i < qlen ? i : qlen - 1u];                    // (unconditional loads travel together; qlen >= 1: the newline)
+    }
+}
+
+template <int NG>
+__device__ __forceinline__ void prof_short_bytes(const uint8_t by[NG], uint32_t len, unsigned int *bins, unsigned int *copies, bool spread, int lane)
+{
+#pragma unroll
+    for (int k = 0; k < NG; k++) {
+        if (64u * (uint32_t)k >= len) break;
+        prof_byte(bins, copies, spread, by[k], 64u * (uint32_t)k + (uint32_t)lane < len, lane);
+    }
+}
+
+// the engine's trim of a short score line at one cutoff: kvq_trim_records' loop (the line's newline is fed too: it closes
+// the last run when it is below the cutoff)
+template <int NG>
+__device__ __forceinline__ int prof_short_trim(const uint8_t by[NG], uint32_t qlen, int amin, int lane)
+{
+    RunState st; st.in_run = 1; st.run_start = 0; st.best = 0; st.best_start = 0;
+#pragma unroll
+    for (int k = 0; k < NG; k++) {
+        const uint32_t o = 64u * (uint32_t)k;
+        if (o >= qlen) break;
+        const uint64_t good = __ballot(o + (uint32_t)lane < qlen && (int)(int8_t)by[k] >= amin);
+        run_feed(st, good, (qlen - o) < 64u ? (int)(qlen - o) : 64, o);
+    }
+    return st.best;
+}
+
+// Grid-stride over waves, KVQ_TRIM_RPW consecutive records a wave (a wave a record).  prof: the profile array of
+// include/kvarq_hip.h.  Dynamic LDS: KvqProfLds::words(C.n, spread) words.
+extern "C" __global__ void __launch_bounds__(256)
+kvq_profile_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__ nl4, uint32_t nrec, KvqProfileCuts C,
+                    uint32_t spread_, unsigned long long *__restrict__ prof)
+{
+    KVQ_BESIDE_SCAN();
+    extern __shared__ unsigned int prof_lds[];
+    const bool spread = spread_ != 0u;
+    const int ncut = C.n;
+    const uint32_t nwords = KvqProfLds::words(ncut, spread);
+    for (uint32_t i = threadIdx.x; i < nwords; i += blockDim.x) prof_lds[i] = 0u;
+    __syncthreads();
+    unsigned int *const score = prof_lds + KvqProfLds::SCORE, *const base = prof_lds + KvqProfLds::BASE, *const raw = prof_lds + KvqProfLds::RAW;
+    unsigned int *const trimmed = prof_lds + KvqProfLds::TRIM, *const sc = prof_lds + KvqProfLds::scalars(ncut);
+    unsigned int *const score_copies = prof_lds + KvqProfLds::copies(ncut), *const base_copies = score_copies + 256 * KVQ_PROF_COPIES;
+
+    const int lane = kvq_lane();
+    unsigned long long nbase = 0, nscore = 0;          // bytes on the bases / score lines of this wave's records
+    uint32_t mine = 0, mism = 0, longest = 0;
+    for (uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6); (uint64_t)wave * KVQ_TRIM_RPW < nrec; wave += gridDim.x * 4u) {
+        const uint32_t g_begin = wave * KVQ_TRIM_RPW;
+        for (uint32_t g = g_begin; g < g_begin + KVQ_TRIM_RPW && g < nrec; g++) {
+            const uint32_t n0 = nl4[4 * (size_t)g], n1 = nl4[4 * (size_t)g + 1], n2 = nl4[4 * (size_t)g + 2], n3 = nl4[4 * (size_t)g + 3];
+            const uint8_t *bline = data + n0 + 1u, *sline = data + n2 + 1u;
+            const uint32_t L = n1 - n0 - 1u, Q = n3 - n2 - 1u;
+            mine++; nbase += L; nscore += Q; mism += L != Q;
+            longest = L + 1u > longest ? L + 1u : longest;
+            if (lane == 0) atomicAdd(&raw[L < KVQ_PROF_RAW_BINS - 1u ? L : KVQ_PROF_RAW_BINS - 1u], 1u);
+            // the bases line
+            if (L >= 1024u) prof_long_bytes(bline, L, base, base_copies, spread, lane);
+            else if (L >= 256u) { uint8_t by[16]; prof_short_load<16>(bline, L + 1u, lane, by); prof_short_bytes<16>(by, L, base, base_copies, spread, lane); }
+            else { uint8_t by[4]; prof_short_load<4>(bline, L + 1u, lane, by); prof_short_bytes<4>(by, L, base, base_copies, spread, lane); }
+            // the score line, and what the trim leaves of it at every cutoff (add_rl: a read of 1024 and more in no bin)
+            auto count = [&](int k, int rl) {
+                if (lane == 0) {
+                    if (rl < KVQ_RL_BINS) atomicAdd(&trimmed[(uint32_t)k * KVQ_RL_BINS + (uint32_t)rl], 1u);
+                    atomicMax(&sc[KvqProfLds::S_CUT_LONGEST + k], (unsigned int)rl + 1u);
+                }
+            };
+            if (Q >= 1024u) {
+                prof_long_bytes(sline, Q, score, score_copies, spread, lane);
+                for (int k = 0; k < ncut; k++) {
+                    const int amin = prof_amin(C, k);
+                    // (kvq_long_line_run closes the last run at the end of what it is given: where the newline is no low
+                    // byte, the line ends for it at its last low byte, which closes the last run that counts)
+                    uint32_t end = Q; bool closed = true;
+                    if ('\n' >= amin) { const uint32_t behind = prof_last_low(sline, Q, amin, lane); closed = behind > 0u; end = behind - 1u; }
+                    int best = 0; uint32_t bstart = 0;
+                    if (closed) kvq_long_line_run(sline, end, amin, lane, best, bstart);
+                    count(k, best);
+                }
+            } else if (Q >= 256u) {
+                uint8_t by[16]; prof_short_load<16>(sline, Q + 1u, lane, by);
+                prof_short_bytes<16>(by, Q, score, score_copies, spread, lane);
+                for (int k = 0; k < ncut; k++) count(k, prof_short_trim<16>(by, Q + 1u, prof_amin(C, k), lane));
+            } else {
+                uint8_t by[4]; prof_short_load<4>(sline, Q + 1u, lane, by);
+                prof_short_bytes<4>(by, Q, score, score_copies, spread, lane);
+                for (int k = 0; k < ncut; k++) count(k, prof_short_trim<4>(by, Q + 1u, prof_amin(C, k), lane));
+            }
+        }
+    }
+    if (lane == 0 && mine) {
+        atomicAdd(&sc[KvqProfLds::S_RECORDS], mine);
+        if (mism) atomicAdd(&sc[KvqProfLds::S_MISMATCH], mism);
+        atomicMax(&sc[KvqProfLds::S_LONGEST], longest);
+        atomicAdd(&prof[KVQ_PROF_BASE_LINE_BYTES], nbase);
+        atomicAdd(&prof[KVQ_PROF_SCORE_LINE_BYTES], nscore);
+    }
+    __syncthreads();
+    // the workgroup's bins that are not zero -> the profile; the maxima as maxima
+    for (uint32_t i = threadIdx.x; i < 512u; i += blockDim.x) {
+        unsigned int v = prof_lds[i];
+        if (spread)
+            for (uint32_t c = 0; c < KVQ_PROF_COPIES; c++) v += score_copies[i * KVQ_PROF_COPIES + c];      // (the bases' copies lie behind the scores')
+        if (v) atomicAdd(&prof[KVQ_PROF_SCORE_BYTES + i], (unsigned long long)v);
+    }
+    for (uint32_t i = threadIdx.x; i < KVQ_PROF_RAW_BINS; i += blockDim.x)
+        if (raw[i]) atomicAdd(&prof[KVQ_PROF_RAW_LENGTHS + i], (unsigned long long)raw[i]);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)ncut * KVQ_RL_BINS; i += blockDim.x)
+        if (trimmed[i]) atomicAdd(&prof[KVQ_PROF_CUTOFFS + (i / KVQ_RL_BINS) * KVQ_PROF_CUT_WORDS + 1u + (i % KVQ_RL_BINS)], (unsigned long long)trimmed[i]);
+    if (threadIdx.x == 0) {
+        if (sc[KvqProfLds::S_RECORDS]) atomicAdd(&prof[KVQ_PROF_RECORDS], (unsigned long long)sc[KvqProfLds::S_RECORDS]);
+        if (sc[KvqProfLds::S_MISMATCH]) atomicAdd(&prof[KVQ_PROF_MISMATCHED], (unsigned long long)sc[KvqProfLds::S_MISMATCH]);
+        if (sc[KvqProfLds::S_LONGEST]) atomicMax(&prof[KVQ_PROF_LONGEST], (unsigned long long)sc[KvqProfLds::S_LONGEST]);
+    }
+    if (threadIdx.x < (uint32_t)ncut && sc[KvqProfLds::S_CUT_LONGEST + threadIdx.x])
+        atomicMax(&prof[KVQ_PROF_CUTOFFS + threadIdx.x * KVQ_PROF_CUT_WORDS], (unsigned long long)sc[KvqProfLds::S_CUT_LONGEST + threadIdx.x]);
+}

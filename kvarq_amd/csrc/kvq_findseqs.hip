@@ -170,9 +170,13 @@ static int findseqs_pass(kvq_scan *s, Route route, const char *const *files, int
 }
 
 static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
-                               const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags)
+                               const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags, const kvq_find_opts *opts = nullptr)
 {
     kvq_clear_error();
+    if ((flags & KVQ_FIND_PROFILE) && (!opts || opts->n_cutoffs < 0 || opts->n_cutoffs > KVQ_PROFILE_MAX_CUTOFFS)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: at most %d cutoffs", KVQ_PROFILE_MAX_CUTOFFS);
+        return nullptr;
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -205,7 +209,10 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         t = kvq_table_create(seqs, seqlens, nseq, nullptr);
         s = t ? kvq_scan_create(t, nullptr) : nullptr;
     }
-    if (s && kvq_scan_set_records(s, (flags & KVQ_FIND_RECORDS) ? 1 : 0)) { kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr; }
+    if (s && (kvq_scan_set_records(s, (flags & KVQ_FIND_RECORDS) ? 1 : 0) ||
+              kvq_scan_set_profile(s, opts ? opts->cutoffs : nullptr, (flags & KVQ_FIND_PROFILE) ? opts->n_cutoffs : -1))) {
+        kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
+    }
     const double tf1 = now_ms();
     // the two pinned host buffers outlive the call: pinning and unpinning 130 MB costs more than
     // streaming a 1 GB file through them (only one findseqs runs at a time, g_running)
@@ -279,7 +286,16 @@ extern "C" kvq_scan *kvq_findseqs(const char *const *files, int32_t nfiles,
 extern "C" kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
                                      const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags)
 {
-    return findseqs_impl(files, nfiles, seqs, seqlens, nseq, flags);
+    kvq_find_opts o; memset(&o, 0, sizeof(o));
+    o.size = (uint32_t)sizeof(o); o.flags = flags & ~KVQ_FIND_PROFILE;       // (the profile has cutoffs: kvq_findseqs_opts)
+    return kvq_findseqs_opts(files, nfiles, seqs, seqlens, nseq, &o);
+}
+
+extern "C" kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
+                                       const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts)
+{
+    if (opts && opts->size < sizeof(kvq_find_opts)) { kvq_clear_error(); kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: bad size"); return nullptr; }
+    return findseqs_impl(files, nfiles, seqs, seqlens, nseq, opts ? opts->flags : 0u, opts);
 }
 
 // destroy a scan returned by kvq_findseqs together with the table it created

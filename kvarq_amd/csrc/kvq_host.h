@@ -184,8 +184,8 @@ struct kvq_scan {
     hipEvent_t ev_chain = nullptr;       // this scan's last seed-filter launch and its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles: what the next scan of the process waits for)
     int64_t parsed = 0, total = 0;
     // timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_free;     // ev_free: pairs of earlier scans, reused
-    double ms_all = 0, ms_main = 0; int64_t main_launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_prof, ev_free;     // ev_prof: around kvq_profile_records; ev_free: pairs of earlier scans, reused
+    double ms_all = 0, ms_main = 0, ms_prof = 0; int64_t main_launches = 0;
     // results: ordered and laid out on the device (kernels_results.hip), one copy into pinned host memory
     DevBuf d_sort_tmp, d_sorted, d_result, d_order, d_finish;   // d_order: bucket arrays of the ordering; d_finish: KvqFinishState
     uint32_t order_nb_max = 0;                    // the bucket arrays in d_order are laid out for this many buckets
@@ -211,6 +211,11 @@ struct kvq_scan {
     uint64_t rec_tail_n = 0, rec_tail_b = 0;      // what the tail fetched ahead of time (offsets / lengths of that many hits, that many store bytes)
     uint64_t rec_spec_n = 4096, rec_spec_b = 1u << 20;   // ... guessed from the last scan of this handle
     int64_t rec_store_bytes = 0;                  // store bytes of the finished scan
+    // the profile of the input (kvq_scan_set_profile, kvq_profile.hip): the device array every batch's kvq_profile_records adds to,
+    // its pinned landing buffer, the finished scan's copy
+    bool profile_on = false; int32_t prof_ncut = 0; uint8_t prof_cuts[KVQ_PROFILE_MAX_CUTOFFS] = { 0 };
+    DevBuf d_prof; int64_t *pin_prof = nullptr; size_t pin_prof_cap = 0;
+    std::vector<int64_t> h_prof;
 };
 
 // kernels_seeded.hip

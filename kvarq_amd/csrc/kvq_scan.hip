@@ -88,6 +88,7 @@ static int reset_device_state(kvq_scan *s)
     hipLaunchKernelGGL(kvq_reset_state, dim3(256), dim3(256), 0, s->stream, (unsigned long long *)s->d_small.p, KvqSmall::BYTES / 8,
                        s->d_ctr, (size_t)s->t->ctr_len, s->d_covdiff.as<unsigned long long>(), (size_t)s->t->bases + (size_t)s->t->nseq + 1);
     KVQ_HIP(hipGetLastError());
+    if (s->profile_on) { const int rc = profile_clear(s); if (rc) return rc; }
     if (s->records_on) return records_prepare(s);
     return KVQ_OK;
 }
@@ -213,7 +214,7 @@ static void chain_forget(const kvq_scan *s)
 // timing events are kept for the next scan of the same handle (creating a pair costs several microseconds)
 static void drop_events(kvq_scan *s, bool destroy = false)
 {
-    for (auto *v : { &s->ev_all, &s->ev_main }) { s->ev_free.insert(s->ev_free.end(), v->begin(), v->end()); v->clear(); }
+    for (auto *v : { &s->ev_all, &s->ev_main, &s->ev_prof }) { s->ev_free.insert(s->ev_free.end(), v->begin(), v->end()); v->clear(); }
     if (destroy) {
         chain_forget(s);
         for (auto &e : s->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -235,7 +236,8 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
     if (s->ev_chain) (void)hipEventDestroy(s->ev_chain);
     if (s->pin_rec) pinned_give(s->pin_rec, s->pin_rec_cap);
-    DevBuf *bufs[] = { &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
+    if (s->pin_prof) pinned_give(s->pin_prof, s->pin_prof_cap);
+    DevBuf *bufs[] = { &s->d_prof, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
                        &s->d_rec_start, &s->d_read_off, &s->d_read_len, &s->d_arena, &s->d_blob, &s->d_small, &s->d_stage, &s->d_stage_b };
     for (DevBuf *b : bufs) b->release();
     s->pool.release();
@@ -270,7 +272,7 @@ extern "C" int32_t kvq_scan_reset(kvq_scan *s)
     drop_events(s);
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     s->batches.clear(); s->host_batches = false; s->host_pending = -1; s->copied_pending = false; s->parsed = 0; s->total = 0;
-    s->ms_all = s->ms_main = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->n_hits = 0;
+    s->ms_all = s->ms_main = s->ms_prof = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->n_hits = 0;
     s->tail_pending = false;
     s->pool.used = 0;
     const int rr = reset_device_state(s);
@@ -310,6 +312,7 @@ struct BatchRun {
     const uint32_t *d_co;            // the chunk offsets in the device half of the pool
     std::vector<uint32_t> sb;        // the first segment (KVQ_SEG_BYTES) of every chunk; sb[nchunks]: segments of the batch
     uint32_t maxseg, maxchunk;       // the most segments / bytes a chunk has
+    int64_t nrec = -1;               // records of the batch, once index_records has run for it (exhaustive_pass; the profile)
 };
 
 // chunk table: written into the pinned half of the pool, copied to its device half (async)
@@ -341,13 +344,13 @@ static int chunk_table(kvq_scan *s, BatchRun &B, const int64_t *chunk_off)
     return KVQ_OK;
 }
 
-// The exhaustive pass over every record of the batch, for the n_exh sequences of d_exh (none: only the records are counted,
-// when no seed-filter launch has done it).  It needs one host round trip (records per chunk) to size its record arrays.
-static int exhaustive_pass(kvq_scan *s, const BatchRun &B, const int32_t *d_exh, int32_t n_exh, bool hist_done)
+// The exact record index of a batch, from its newline counts: nl4 / rec_start of every complete record of every chunk (d_nl4,
+// d_rec_start), B.nrec of them.  It needs one host round trip (records per chunk) to size its arrays.  Its users: the
+// exhaustive pass and the profile (which takes the exhaustive pass's index where a batch has one).
+static int index_records(kvq_scan *s, BatchRun &B)
 {
     int rc;
     const uint8_t *d_data = B.d_data; const int64_t nchunks = B.nchunks; const uint32_t *d_co = B.d_co; const uint64_t segs = B.sb[nchunks];
-    if (n_exh > 0) s->path_bits |= 2;
     if ((rc = s->d_seg_base.ensure(B.sb.size() * 4)) || (rc = s->d_seg_cnt.ensure((size_t)(segs + 1) * 4)) ||
         (rc = s->d_chunk_nrec.ensure((size_t)(nchunks + 1) * 4)) || (rc = s->d_rec_base.ensure((size_t)(nchunks + 1) * 4))) return rc;
     KVQ_HIP(hipMemcpyAsync(s->d_seg_base.p, B.sb.data(), B.sb.size() * 4, hipMemcpyHostToDevice, s->stream));
@@ -365,9 +368,9 @@ static int exhaustive_pass(kvq_scan *s, const BatchRun &B, const int32_t *d_exh,
     uint64_t R = 0;
     for (int64_t c = 0; c < nchunks; c++) { rbase[c] = (uint32_t)R; R += nrec[c]; }
     rbase[nchunks] = (uint32_t)R;
+    B.nrec = (int64_t)R;
     if (R == 0) return KVQ_OK;
-    if ((rc = s->d_nl4.ensure((size_t)R * 16)) || (rc = s->d_rec_start.ensure((size_t)R * 4)) ||
-        (rc = s->d_read_off.ensure((size_t)R * 4)) || (rc = s->d_read_len.ensure((size_t)R * 4))) return rc;
+    if ((rc = s->d_nl4.ensure((size_t)R * 16)) || (rc = s->d_rec_start.ensure((size_t)R * 4))) return rc;
     KVQ_HIP(hipMemcpyAsync(s->d_rec_base.p, rbase.data(), rbase.size() * 4, hipMemcpyHostToDevice, s->stream));
     KVQ_HIP(hipStreamSynchronize(s->stream));
     for (int64_t c0 = 0; c0 < nchunks; c0 += 32768) {
@@ -377,6 +380,20 @@ static int exhaustive_pass(kvq_scan *s, const BatchRun &B, const int32_t *d_exh,
                            s->d_chunk_nrec.as<uint32_t>() + c0, s->d_rec_base.as<uint32_t>() + c0,
                            s->d_nl4.as<uint32_t>(), s->d_rec_start.as<uint32_t>());
     }
+    return KVQ_OK;
+}
+
+// The exhaustive pass over every record of the batch, for the n_exh sequences of d_exh (none: only the records are counted,
+// when no seed-filter launch has done it).
+static int exhaustive_pass(kvq_scan *s, BatchRun &B, const int32_t *d_exh, int32_t n_exh, bool hist_done)
+{
+    int rc;
+    const uint8_t *d_data = B.d_data;
+    if (n_exh > 0) s->path_bits |= 2;
+    if ((rc = index_records(s, B))) return rc;
+    const uint64_t R = (uint64_t)B.nrec;
+    if (R == 0) return KVQ_OK;
+    if ((rc = s->d_read_off.ensure((size_t)R * 4)) || (rc = s->d_read_len.ensure((size_t)R * 4))) return rc;
     const uint32_t per_block = 4 * 16;       // KVQ_TRIM_RPW records per wave
     hipLaunchKernelGGL(kvq_trim_records, dim3((uint32_t)((R + per_block - 1) / per_block)), dim3(256), 0, s->stream, B.P, d_data,
                        B.fpos_base, (uint32_t)R, KvqDevCount{ nullptr, 0, 0, nullptr }, s->d_nl4.as<uint32_t>(), s->d_rec_start.as<uint32_t>(),
@@ -476,6 +493,18 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
     if ((!B.use_seeded || n_exh > 0) && (rc = exhaustive_pass(s, B, d_exh, n_exh, B.use_seeded))) return rc;
     if (B.use_seeded && s->cur_ntiles) redo_skipped_tiles(s, B);      // (a batch of empty chunks has scanned no tile: nothing was skipped, and the redo's counts are the LAST launch's)
     if ((rc = close_batch(s, B))) return rc;
+    // the profile: every batch once, by its first pass (the redo of a batch that failed validation leaves it alone, and so does
+    // the redo of skipped tiles), from the exact index -- the exhaustive pass's where the batch has one; a seeded batch waits
+    // on the host once for its own.  In front of the closing event: what guards the batch's text guards this pass too
+    if (s->profile_on && !exhaustive_only) {
+        if (B.nrec < 0 && (rc = index_records(s, B))) return rc;
+        if (B.nrec > 0) {
+            if ((rc = new_event_pair(s, s->ev_prof))) return rc;
+            KVQ_HIP(hipEventRecord(s->ev_prof.back().first, s->stream));
+            if ((rc = profile_enqueue(s, d_data, (uint64_t)B.nrec))) return rc;
+            KVQ_HIP(hipEventRecord(s->ev_prof.back().second, s->stream));
+        }
+    }
     KVQ_HIP(hipEventRecord(s->ev_all.back().second, s->stream));
     KVQ_HIP(hipGetLastError());
     if (g_timing) fprintf(stderr, "run_batch host %.3f ms\n", now_ms() - tb0);

@@ -112,7 +112,7 @@ PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
 PATH_DEVICE_BAM = 0x40                             # kvq_scan_path bit 6
 
 
-def findseqs(fname, sequences, *, inflate='host', records=False):
+def findseqs(fname, sequences, *, inflate='host', records=False, profile=None):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
@@ -139,7 +139,13 @@ def findseqs(fname, sequences, *, inflate='host', records=False):
     stats, counters and records are those of a scan of that text, and file_pos counts
     its bytes.  The records are decoded on the GPU whatever ``inflate`` says
     (last_inflate() == 'device_bam', last_bam_report() what the route did); a call that
-    mixes BAM and other files raises IOError."""
+    mixes BAM and other files raises IOError.
+
+    profile=<cutoffs> (not in the reference): the dict gains 'profile', a
+    ``kvarq_amd.profile.Profile`` of the whole input -- score and base bytes, read lengths,
+    and what the quality trim leaves at each cutoff (characters, bytes or ints, at most 8;
+    ``True``: the configured Amin alone) -- taken on the GPU during the scan (DESIGN
+    section 13).  ``sequences`` may then be empty."""
     import os, time
     global _last_inflate
     if inflate not in INFLATE_FLAGS:
@@ -180,7 +186,13 @@ def findseqs(fname, sequences, *, inflate='host', records=False):
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
-    if inflate == 'host' and not records:
+    if profile is not None:
+        from . import profile as profile_
+        cuts = profile_.as_cutoffs(profile)
+        opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE,
+                             len(cuts), (C.c_uint8 * 8)(*cuts))
+        h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opts))
+    elif inflate == 'host' and not records:
         h = L.kvq_findseqs(farr, len(bfiles), sarr, lens, n)
     else:
         h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0))
@@ -225,6 +237,8 @@ def findseqs(fname, sequences, *, inflate='host', records=False):
                            'they are trimmed to nothing' % noqual)
         if records:
             out['records'] = _records(L, h, nh, as_str)
+        if profile is not None:
+            out['profile'] = profile_.from_scan(L, h)
         return out
     finally:
         if h:

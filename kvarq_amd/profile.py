@@ -1,0 +1,205 @@
+"""
+The profile of a whole input, taken on the GPU during the scan (include/kvarq_hip.h): which bytes
+the score and bases lines hold, how long the reads are, and what the engine's quality trim leaves of them at a few
+cutoffs -- the questions the reference answers from a sample of the file with ``kvarq show -Q q -i``
+(kvarq/cli.py:201-221) and in ``Fastq.__init__``, answered here for every record.
+
+``profile(fnames, cutoffs)`` scans files with no sequences; ``engine.findseqs(..., profile=...)``,
+``scan.Scanner(..., profile=...)``, ``Fastq.profile()``, ``Bam.profile()`` and ``Analyser.scan(..., profile=...)``
+take the profile along with a scan.  ``profile_host`` is the CPU twin of the kernel (the definition in running code
+and test infrastructure, not a fallback).  ``python -m kvarq_amd.profile FILE [-Q q ...]`` prints the summary.
+
+Out of scope: per-cycle quality, profiles across ranks, and what ``Fastq`` guesses by default.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .fastq import ASCII, PhredScale, FastqFileFormatException
+
+MAX_CUTOFFS = 8
+# the layout of the flat array (include/kvarq_hip.h)
+RECORDS, BASE_LINE_BYTES, SCORE_LINE_BYTES, MISMATCHED, LONGEST = 0, 1, 2, 3, 4
+SCORE_BYTES, BASE_BYTES, RAW_LENGTHS, RAW_BINS, CUTOFFS, CUT_WORDS = 8, 264, 520, 1025, 1545, 1025
+
+
+def profile_len(ncut):
+    return CUTOFFS + ncut * CUT_WORDS
+
+
+def as_cutoffs(cutoffs, amin=None):
+    """an iterable of cutoffs (characters, bytes or ints) as a list of byte values; ``True``: the configured Amin alone"""
+    if cutoffs is True:
+        if amin is None:
+            from . import engine
+            amin = engine.get_config()['Amin']
+        cutoffs = [amin]
+    if isinstance(cutoffs, (str, bytes, bytearray)):
+        cutoffs = list(cutoffs)
+    out = []
+    for c in cutoffs:
+        if isinstance(c, str):
+            c = c.encode('latin-1')
+        if isinstance(c, (bytes, bytearray)):
+            if len(c) != 1:
+                raise TypeError('a cutoff must be a single character')
+            c = c[0]
+        c = int(c)
+        if not -128 <= c <= 255:
+            raise ValueError('a cutoff must be a byte value')
+        out.append(c & 0xFF)
+    if len(out) > MAX_CUTOFFS:
+        raise ValueError('at most %d cutoffs' % MAX_CUTOFFS)
+    return out
+
+
+def _cut_array(cutoffs):
+    return (C.c_uint8 * MAX_CUTOFFS)(*cutoffs)
+
+
+class Profile(object):
+    """a finished profile: ``records``, ``score_bytes`` / ``base_bytes`` (256 counts each), ``raw_lengths`` (1025 bins,
+    the last one holding the lines of 1024 bytes and more), ``mismatched`` (records whose score and bases lines differ
+    in length), ``longest`` (the longest bases line, -1: none), ``cutoffs`` (byte values), ``words`` (the flat array)"""
+
+    def __init__(self, words, cutoffs):
+        self.cutoffs = list(cutoffs)
+        self.words = np.array(words, dtype=np.int64)
+        assert self.words.shape == (profile_len(len(self.cutoffs)),)
+        w = self.words
+        self.records, self.base_line_bytes, self.score_line_bytes = int(w[RECORDS]), int(w[BASE_LINE_BYTES]), int(w[SCORE_LINE_BYTES])
+        self.mismatched, self.longest = int(w[MISMATCHED]), int(w[LONGEST]) - 1
+        self.score_bytes = w[SCORE_BYTES:SCORE_BYTES + 256]
+        self.base_bytes = w[BASE_BYTES:BASE_BYTES + 256]
+        self.raw_lengths = w[RAW_LENGTHS:RAW_LENGTHS + RAW_BINS]
+
+    def __eq__(self, other):
+        return isinstance(other, Profile) and self.cutoffs == other.cutoffs and (self.words == other.words).all()
+
+    def __ne__(self, other):
+        return not self == other
+
+    def _cut(self, cutoff):
+        c = as_cutoffs([cutoff])[0]
+        if c not in self.cutoffs:
+            raise KeyError('no such cutoff in this profile: %r' % (cutoff,))
+        at = CUTOFFS + self.cutoffs.index(c) * CUT_WORDS
+        return int(self.words[at]) - 1, self.words[at + 1:at + CUT_WORDS]
+
+    def readlengths(self, cutoff):
+        """the quality-trimmed read lengths at ``cutoff`` in the shape of ``stats['readlengths']``: what a scan with
+        ``Amin = cutoff`` reports (reads of 1024 and more in no bin, but in the tuple's length)"""
+        longest, bins = self._cut(cutoff)
+        return tuple(int(bins[i]) if i < _lib.MAX_READLENGTH else 0 for i in range(longest + 1))
+
+    def score_range(self):
+        """the lowest and the highest score character as indices into ``ASCII`` -- what
+        ``Fastq.min_max_score_check_file`` returns, from every record (a '\\r' at the end of a line is no score);
+        (999, -999) when there is none"""
+        seen = [b for b in np.nonzero(self.score_bytes)[0].tolist() if b != 13]
+        return (seen[0] - 33, seen[-1] - 33) if seen else (999, -999)
+
+    def variants(self):
+        """the vendor scales that hold every score of the input (``PhredScale.holding``)"""
+        return PhredScale.holding(*self.score_range())
+
+    def dQ(self):
+        """the PHRED offset as ``Fastq`` states it (the offset of Q = 0 in ``ASCII``), by ``Fastq._scale``'s rules:
+        FastqFileFormatException when no scale fits or the fitting ones disagree (Sanger / Illumina 1.3+)"""
+        fitting = self.variants()
+        offsets = {PhredScale.offset(name) for name in fitting}
+        if not offsets:
+            raise FastqFileFormatException('could not find any suitable fastq vendor variant')
+        if len(offsets) > 1:
+            raise FastqFileFormatException('cannot determine dQ with guessed vendor variants "%s"' % fitting)
+        return offsets.pop()
+
+    def mean_quality(self, dQ=None):
+        """the mean PHRED score over every score character ('\\r' left out); ``dQ`` None: :meth:`dQ`"""
+        dQ = self.dQ() if dQ is None else dQ
+        n = self.score_bytes.copy(); n[13] = 0
+        total = int(n.sum())
+        return float((n * (np.arange(256) - 33 - dQ)).sum()) / total if total else float('nan')
+
+    def kept(self, cutoff, minreadlength):
+        """the share of records whose trimmed read the length gate lets through (workhorse.c:1100)"""
+        longest, bins = self._cut(cutoff)
+        if not self.records:
+            return 0.0
+        if minreadlength > _lib.MAX_READLENGTH:
+            raise ValueError('lengths of %d and more are not binned' % _lib.MAX_READLENGTH)
+        dropped = int(bins[:max(int(minreadlength), 0)].sum())
+        return (self.records - dropped) / float(self.records)
+
+    def summary(self):
+        lines = ['records=%d mismatched=%d longest=%d' % (self.records, self.mismatched, self.longest)]
+        lo_, hi = self.score_range()
+        try:
+            lines.append('dQ=%d' % self.dQ())
+        except FastqFileFormatException as e:
+            lines.append('dQ=? (%s)' % e)
+        span = '?' if lo_ > hi else '%r..%r' % (chr(lo_ + 33), chr(hi + 33))
+        lines.append('variants=%s scores=%s' % (self.variants(), span))
+        for c in self.cutoffs:
+            rl = self.readlengths(c)
+            n = sum(rl)
+            mean = sum(i * v for i, v in enumerate(rl)) / float(n) if n else 0.0
+            lines.append('cutoff=%s readlengths: longest=%d mean=%.1f binned=%d' % (repr(chr(c)) if 33 <= c < 127 else hex(c), len(rl) - 1, mean, n))
+        return '\n'.join(lines)
+
+    def as_dict(self):
+        """what ``Analyser.encode`` stores"""
+        return {'records': self.records, 'mismatched': self.mismatched, 'longest': self.longest,
+                'score_bytes': {int(b): int(self.score_bytes[b]) for b in np.nonzero(self.score_bytes)[0]},
+                'base_bytes': {int(b): int(self.base_bytes[b]) for b in np.nonzero(self.base_bytes)[0]},
+                'readlengths': {str(c): list(self.readlengths(c)) for c in self.cutoffs}}
+
+
+def from_scan(L, h):
+    """the profile of a finished scan object (kvq_scan_profile), None when it keeps none"""
+    cuts = (C.c_uint8 * MAX_CUTOFFS)()
+    n = L.kvq_scan_profile_cutoffs(h, cuts)
+    ptr = L.kvq_scan_profile(h)
+    if n < 0 or not ptr:
+        return None
+    return Profile(np.ctypeslib.as_array(ptr, shape=(profile_len(n),)).copy(), list(cuts)[:n])
+
+
+def profile_host(text, cutoffs=(), chunk_off=None):
+    """the CPU twin (kvq_profile_host) over a text in host memory; chunk_off None: the reader's chunk cuts"""
+    from . import scan
+    cuts = as_cutoffs(cutoffs)
+    arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
+    co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
+    out = np.zeros(profile_len(len(cuts)), dtype=np.int64)
+    rc = _lib.lib().kvq_profile_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)),
+                                     len(co) - 1, _cut_array(cuts), len(cuts), out.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc:
+        raise RuntimeError(_lib.last_error()[1])
+    return Profile(out, cuts)
+
+
+def profile(fnames, cutoffs=True, inflate='host'):
+    """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences"""
+    from . import engine
+    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs)['profile']
+
+
+def main(argv=None):
+    import argparse
+    from . import engine
+    ap = argparse.ArgumentParser(prog='python -m kvarq_amd.profile', description='profile of a FastQ / BAM file, taken on the GPU')
+    ap.add_argument('files', nargs='+')
+    ap.add_argument('-Q', '--quality', type=int, action='append', help='PHRED cutoff(s); default: the configured Amin')
+    ap.add_argument('--inflate', default='host', choices=sorted(engine.INFLATE_FLAGS))
+    a = ap.parse_args(argv)
+    p = profile(a.files, cutoffs=True, inflate=a.inflate)
+    if a.quality:
+        dQ = p.dQ()
+        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate)
+    print(p.summary())
+
+
+if __name__ == '__main__':
+    main()

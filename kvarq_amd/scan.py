@@ -96,7 +96,7 @@ class Scanner(object):
     ``finish`` raises ``RescanRequired`` and the caller, who has the data, resets and feeds again; a caller with
     a re-readable source passes ``replay=callable`` (called with the scanner after ``reset()``) instead."""
 
-    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False):
+    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None):
         self.table = table
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
@@ -104,6 +104,12 @@ class Scanner(object):
         self.records = bool(records)     # keep the FastQ record of every hit (kvq_scan_set_records; kept across reset)
         if self.records:
             _check(_lib.lib().kvq_scan_set_records(self.h, 1))
+        # profile the input at these cutoffs (kvarq_amd.profile.as_cutoffs; True: the table's Amin); kept across reset
+        self.profile = None
+        if profile is not None:
+            from . import profile as profile_
+            self.profile = profile_.as_cutoffs(profile, amin=bytes([table.config.Amin & 0xFF]))
+            _check(_lib.lib().kvq_scan_set_profile(self.h, (C.c_uint8 * 8)(*self.profile), len(self.profile)))
         self._host_batches = []          # copies of what scan_host was given since the last reset (fed again when the hit arena overflows)
         self._device_batches = []        # what scan_device was given since the last reset (the caller's device memory: nothing is copied)
         self._retained, self._retain_limit, self._replay = 0, (0 if replay is not None else retain_limit), replay
@@ -188,6 +194,10 @@ class Scanner(object):
             out.update(self._hits_dict())
             if self.records:
                 out['records'] = self._records()
+        if self.profile is not None:
+            from . import profile as profile_
+            out['profile'] = profile_.from_scan(L, self.h)
+            out['profile_kernel_ms'] = L.kvq_scan_profile_kernel_ms(self.h)
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
