@@ -263,12 +263,14 @@ void    kvq_scan_force_exhaustive(kvq_scan *s, int32_t on);
  * launcher's own choice, a host function of its inputs: the table's seed length, stride and density (its seed index
  * expects more candidates per read than a wave's queue holds), the average record and the tile the head of the text
  * gave (kvq_tile_for_text), and the KVQ_DBG bits; -1 when no kernel exists for them.  kvq_scan_kernel: the cell of
- * the scan's last seed-filter launch since kvq_scan_create / kvq_scan_reset, 0 = none. */
+ * the scan's last seed-filter launch since kvq_scan_create / kvq_scan_reset, 0 = none.  kvq_scan_grid: the workgroups
+ * of that launch (the tiles of the batch, at most what the device holds at once or what the KVQ_GRID switch allows), 0 = none. */
 #define KVQ_CELL_DENSE  0x1000           /* the draining kernels (always for K < 8) */
 #define KVQ_CELL_DIAG   0x2000           /* the instantiations that honour the KVQ_DBG switches (K < 8 and draining kernels too) */
 #define KVQ_CELL_STAMPS 0x4000           /* the instrumented build (KVQ_DBG bit 16) */
 int32_t kvq_scan_kernel_pick(int32_t k, int32_t stride, int32_t dense, uint32_t rec_bytes, uint32_t tile_bytes, uint32_t dbg);
 int32_t kvq_scan_kernel(const kvq_scan *s);
+int32_t kvq_scan_grid(const kvq_scan *s);
 /* host only: the tile (bytes a workgroup owns) of the seed-filter scan for a text whose first n bytes are given (the
  * library looks at the first 128 KiB of a scan's first batch); *rec_bytes_out, where not NULL, gets the average
  * record among them (0 = fewer than 16 lines) */

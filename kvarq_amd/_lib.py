@@ -111,6 +111,7 @@ PROTOTYPES = {
     'kvq_scan_force_exhaustive': (None, [vp, i32]),
     'kvq_scan_kernel_pick': (i32, [i32, i32, i32, C.c_uint32, C.c_uint32, C.c_uint32]),
     'kvq_scan_kernel': (i32, [vp]),
+    'kvq_scan_grid': (i32, [vp]),
     'kvq_tile_for_text': (C.c_uint32, [vp, C.c_size_t, P(C.c_uint32)]),
     'kvq_comm_unique_id': (i32, [vp]),
     'kvq_comm_create': (vp, [i32, i32, vp]),

@@ -164,6 +164,7 @@ struct kvq_scan {
     unsigned long long *d_blob_n = nullptr, *d_err = nullptr, *d_err_stage = nullptr, *d_stage_ctr = nullptr;
     int path_bits = 0;
     int32_t kernel_cell = 0;           // the kvq_scan_bp instantiation of the last seed-filter launch (kvq_scan_kernel_pick)
+    int32_t kernel_grid = 0;           // ... and its workgroups (kvq_scan_grid)
     std::vector<int64_t> cur_chunk_off;  // chunk offsets of the batch being enqueued
     size_t cur_co_at = 0;                // ... and where run_batch put them in the pool
     size_t cur_skip_at = 0, cur_first_at = 0; uint32_t cur_ntiles = 0;   // the batch's list of skipped tiles, its first-tile table

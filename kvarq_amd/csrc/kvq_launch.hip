@@ -42,6 +42,7 @@ extern "C" int32_t kvq_scan_kernel_pick(int32_t k, int32_t stride, int32_t dense
 }
 
 extern "C" int32_t kvq_scan_kernel(const kvq_scan *s) { return s->kernel_cell; }
+extern "C" int32_t kvq_scan_grid(const kvq_scan *s) { return s->kernel_grid; }
 
 int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, int64_t nbytes,
                       const uint32_t *d_chunk_off, int64_t nchunks, int64_t fpos_base, uint32_t max_chunk_bytes)
@@ -167,7 +168,7 @@ int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, in
         const bool dense = (cell & KVQ_CELL_DENSE) != 0, diag = (cell & KVQ_CELL_DIAG) != 0, stamps = (cell & KVQ_CELL_STAMPS) != 0;
         const BpKernel *const dk = k == 5 ? kernels_k5 : k == 6 ? kernels_k6 : k == 7 ? kernels_k7 : dense ? kernels_dense : kernels_diag;
         const BpKernel kern = diag ? dk[(lg == 2 ? 3 : 0) + si] : kernels_bp[lg == 3 ? 12 + si : lg == 1 ? 15 + si : (lg == 2 ? 6 : 0) + si + (stamps ? 3 : 0)];
-        s->kernel_cell = cell;
+        s->kernel_cell = cell; s->kernel_grid = (int32_t)grid_seeded;
         hipLaunchKernelGGL(kern, dim3(grid_seeded), dim3(ST_THREADS), 0, s->stream, d_args);
     }
     if (timed) KVQ_HIP(hipEventRecord(s->ev_main.back().second, s->stream));

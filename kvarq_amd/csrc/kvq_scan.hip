@@ -272,7 +272,7 @@ extern "C" int32_t kvq_scan_reset(kvq_scan *s)
     drop_events(s);
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     s->batches.clear(); s->host_batches = false; s->host_pending = -1; s->copied_pending = false; s->parsed = 0; s->total = 0;
-    s->ms_all = s->ms_main = s->ms_prof = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->n_hits = 0;
+    s->ms_all = s->ms_main = s->ms_prof = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
     s->tail_pending = false;
     s->pool.used = 0;
     const int rr = reset_device_state(s);

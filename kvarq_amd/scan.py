@@ -218,6 +218,7 @@ class Scanner(object):
         path = L.kvq_scan_path(self.h)
         out['path'] = {'seeded': bool(path & 1), 'exhaustive': bool(path & 2), 'rescanned': bool(path & 4), 'tiles_rescanned': bool(path & 8)}
         out['kernel'] = _lib.kernel_cell(L.kvq_scan_kernel(self.h))      # the scan kernel instantiation of the last seed-filter launch
+        out['grid'] = L.kvq_scan_grid(self.h)                            # ... and its workgroups (0: no such launch)
         return out
 
     def hit_arrays(self):

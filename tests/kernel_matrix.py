@@ -8,13 +8,17 @@ Every text is synthetic background (synth.reads) plus planted records aimed at t
 a lane split goes wrong; each planted record is named after its class (``@P<class>.<n>``) so that the oracle's
 hits can be traced back to it (tests/test_kernel_dispatch.py checks that the workloads are not vacuous,
 tests/test_gpu_kernel_matrix.py runs them on the GPU against the oracle).
+
+``tiles_of`` counts the tiles of a text the way the launcher does, and ``long_walk`` is a text for the launches in
+which one workgroup walks hundreds of tiles (a small KVQ_GRID): see LongWalk.
 """
 import bisect
+import ctypes as C
 import random
 
 import numpy as np
 
-from kvarq_amd import synth
+from kvarq_amd import _lib, scan, synth
 
 CONFIGS = {
     8: dict(maxerrors=2, minoverlap=25, minreadlength=25, Amin='.'),        # the product's configuration
@@ -264,3 +268,89 @@ class Workload(object):
                 if h.seq_nr in self.classes[cls][0]:
                     out[cls] += 1
         return out
+
+
+# ---------------------------------------------------------------------------
+# many tiles per workgroup
+# ---------------------------------------------------------------------------
+
+BP_SHARDS = 64                  # kernels_bp.hip: the shares the tiles of a launch are dealt into
+ST_HIST_TILES = 100             # kernels_seeded.hip: tiles between two flushes of a workgroup's read-length histogram
+ST_RCAP, BP_NLCAP = 512, 1920   # records and newlines a tile's tables hold (beyond: the tile leaves its records to the redo chain)
+BP_WINDOW = 36640 + 4160 + 80   # bytes of text a tile looks at (ST_TILE + ST_OV behind its first byte, ST_PRE in front)
+
+
+def tiles_of(text):
+    """(bytes a tile owns, [tiles of every chunk]) of a text scanned as ONE host batch: kvq_tile_for_text on its first
+    128 KiB, the chunk cuts of kvq_chunk_offsets and kvq_seeded_launch's count per chunk"""
+    arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    tile = _lib.lib().kvq_tile_for_text(arr.ctypes.data, min(arr.nbytes, 128 << 10), None)
+    co = [int(x) for x in scan.chunk_offsets(arr)]
+    return tile, [((b - (a & ~15)) + tile - 1) // tile if b > a else 0 for a, b in zip(co[:-1], co[1:])]
+
+
+def shard_begin(sh, ntiles):
+    """bp_shard_begin: the first tile of share sh"""
+    return sh * ntiles // BP_SHARDS
+
+
+class LongWalk(object):
+    """One text of at least 256 tiles of the most records a tile holds, for launches in which a workgroup walks all of
+    them (KVQ_GRID=1) or a fifth: every share of the tiles holds four or more, so a workgroup stays in its share for
+    several tiles before it looks for another, and a lone workgroup flushes its read-length histogram twice.
+
+    The records are 88 bytes (a two-character name, 40 bases, all scores 'I'), one in a hundred 90 (41 bases): that is
+    about 452 records a tile and 1860 newlines in a tile's window, as close to BP_NLCAP as four-line records of an
+    even read length get (38 bases: 1943) -- BP_NLCAP, not ST_RCAP, is what a tile of short records runs into.  40 is
+    even, so its counts sit in the LOW half of a histogram word (two 16-bit bins a word): without the flush every
+    ST_HIST_TILES tiles a lone workgroup counts all the text's 40-base reads, more than 65535, in that half and the
+    carry lands in the bin of 41.
+
+    Every hundredth read is cut from a template (inside it with 0, 1 or 2 substitutions, or overlapping one of its
+    ends by 10..39 bases), the rest are random bases; the table holds seedable sequences only (40 SNP templates and
+    their reverse complements), so no other kernel sees a record.  Two configurations: K = 5 (draining) and the
+    product's (K = 8, halving); both land on the kernel that works the lane group out per tile."""
+
+    READ, ODD = 40, 41
+    CELLS = ((5, 8, -1, True), (8, 8, -1, False))
+
+    def __init__(self, g=None, n_reads=120000):
+        g = synth.genome() if g is None else g
+        self.plus = [q for q in synth.table(g) if len(q) == 51][:40]
+        self.seqs = synth.both_strands(self.plus)
+        self.cfgs = [dict(CONFIGS[k]) for k, _, _, _ in self.CELLS]
+        for (k, stride, _, dense), cfg in zip(self.CELLS, self.cfgs):
+            e = cfg['maxerrors']
+            assert seed_k(cfg) == k and all(seedable(q, k, e) for q in self.seqs)
+            assert index_stride(self.seqs, k, e) == stride and (k < 8 or index_dense(self.seqs, k, e, stride) == dense)
+        rng = random.Random(20240)
+        bases = np.frombuffer(b'ACGT', dtype=np.uint8)[np.random.RandomState(20240).randint(0, 4, (n_reads, self.ODD))]
+        names = b'0123456789abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ'
+        out, self.n_even, self.n_planted = [], 0, 0
+        for i in range(n_reads):
+            L = self.ODD if i % 100 == 37 else self.READ
+            b = bases[i, :L].tobytes()
+            if i % 100 == 50:
+                j = i // 100
+                q = self.seqs[rng.randrange(len(self.seqs))]
+                if j % 4 < 3:
+                    a = rng.randrange(0, len(q) - L + 1)
+                    b = _mutate(rng, q[a:a + L], rng.sample(range(L), j % 4))
+                else:
+                    ov = 10 + (j // 4) % 30
+                    b = (b[:L - ov] + q[:ov]) if (j // 4) & 1 else (q[-ov:] + b[ov:])
+                self.n_planted += 1
+            self.n_even += L == self.READ
+            out.append(_rec(chr(names[i % 62]) + chr(names[i // 62 % 62]), b))
+        self.n_reads = n_reads
+        self.text = np.frombuffer(b''.join(out), dtype=np.uint8)
+
+
+_long_walk = []
+
+
+def long_walk(g=None):
+    """the LongWalk, built once a process (nothing may change it)"""
+    if not _long_walk:
+        _long_walk.append(LongWalk(g))
+    return _long_walk[0]

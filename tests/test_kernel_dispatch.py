@@ -171,6 +171,8 @@ def test_each_cell_workload_lands_on_its_cell_and_is_not_vacuous(g, cell):
             assert pick(k, stride, dense, rb, tile) == dict(k=k, stride=stride, lg=lg, dense=dense), (i, tile, rb)
         starts, names = w.record_names(text)
         assert len(starts) >= 1000 and text.nbytes >= 20 * tile          # (many tiles, drawn by many workgroups)
+        # (under KVQ_GRID=1 and 5 a workgroup walks all of them, or a fifth: tests/test_gpu_kernel_matrix.py)
+        assert KM.tiles_of(text)[0] == tile and sum(KM.tiles_of(text)[1]) >= 25, (i, KM.tiles_of(text))
         o = O.scan_memory(text, w.seqs, fold=True, nthreads=min(16, os.cpu_count() or 1), **w.cfg)
         assert len(o['hits']) >= 100, (i, len(o['hits']))
         by = w.hits_by_class(text, o['hits'])
@@ -186,3 +188,53 @@ def test_each_cell_workload_lands_on_its_cell_and_is_not_vacuous(g, cell):
         # the refused sequences are met by the exhaustive kernels, the seeded ones by the seed filter
         hit_seqs = set(h.seq_nr % w.np for h in o['hits'])
         assert {w.refused_n, w.refused_short} <= hit_seqs and len(hit_seqs - {w.refused_n, w.refused_short}) > 5
+
+
+def test_the_long_walk_reaches_what_it_is_for(g):
+    """KM.long_walk() is only worth its time if a lone workgroup must flush its read-length histogram, every share of
+    the tiles lets a workgroup stay for a while, and no tile runs out of its tables (a tile that does leaves its records
+    to the redo chain, which proves nothing about the scan kernel)"""
+    if os.environ.get('KVQ_TILE'):
+        pytest.skip('KVQ_TILE sets the tile')
+    w = KM.long_walk(g)
+    text = w.text
+    tile, per_chunk = KM.tiles_of(text)
+    nt = sum(per_chunk)
+    assert tile == choose_tile(w.ODD + 1, 2 * w.READ + 8) == TILE
+    assert nt >= 256 and nt > 2 * KM.ST_HIST_TILES
+    shares = [KM.shard_begin(sh + 1, nt) - KM.shard_begin(sh, nt) for sh in range(KM.BP_SHARDS)]
+    assert sum(shares) == nt and min(shares) >= 4, shares
+    # both configurations land on the kernel that works the lane group out per tile, and every sequence is seeded
+    rb = tile_for_text(text)[1]
+    for (k, stride, lg, dense), cfg in zip(w.CELLS, w.cfgs):
+        assert pick(k, stride, dense, rb, tile) == dict(k=k, stride=stride, lg=lg, dense=dense)
+        assert all(KM.seedable(q, k, cfg['maxerrors']) for q in w.seqs)
+    # no stretch of a tile's bytes holds more record starts than a tile's tables, no window of a tile more newlines
+    nl = np.flatnonzero(text == 10)
+    starts = np.concatenate([[0], nl[3::4][:-1] + 1])
+    assert len(nl) == 4 * w.n_reads and bool((text[starts] == ord('@')).all())
+    per_tile = np.searchsorted(starts, starts + tile) - np.arange(len(starts))
+    per_window = np.searchsorted(nl, nl + KM.BP_WINDOW) - np.arange(len(nl))
+    assert 400 < per_tile.max() <= KM.ST_RCAP and 1800 < per_window.max() <= KM.BP_NLCAP, (per_tile.max(), per_window.max())
+    # with the flush a bin stays below 2^16 between two flushes; without it a lone workgroup's bin of READ runs over
+    # (129 tiles of 510 records, as the kernel's bound is stated: 129 * 510 > 65535 >= 100 * 512), and READ is even: the
+    # carry goes into the bin of READ + 1 in the same word
+    assert KM.ST_HIST_TILES * KM.ST_RCAP <= 65535 < 129 * 510
+    assert KM.ST_HIST_TILES * int(per_tile.max()) <= 65535 < w.n_even and w.READ % 2 == 0 and w.ODD == w.READ + 1
+    assert w.n_reads - w.n_even >= 1000 and w.n_planted >= 1000
+    for cfg in w.cfgs:
+        o = O.scan_memory(text, w.seqs, fold=True, nthreads=min(16, os.cpu_count() or 1), **cfg)
+        rls = o['stats']['readlengths']
+        assert len(rls) == w.ODD + 1 and rls[w.READ] == w.n_even and rls[w.ODD] == w.n_reads - w.n_even
+        assert len(o['hits']) >= 1000
+        # the hits are spread over the walk: every tenth of the text has some
+        tenth = np.bincount([h.file_pos * 10 // text.nbytes for h in o['hits']], minlength=10)
+        assert tenth.min() >= 50, tenth
+
+
+def test_kvq_scan_grid_is_declared_and_bound():
+    """r['grid'] is how the GPU tests see that KVQ_GRID was taken"""
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'kvarq_hip.h')) as f:
+        assert 'int32_t kvq_scan_grid(const kvq_scan *s);' in f.read()
+    assert _lib.PROTOTYPES['kvq_scan_grid'] == _lib.PROTOTYPES['kvq_scan_kernel']
+    assert _lib.lib().kvq_scan_grid.restype is C.c_int32
