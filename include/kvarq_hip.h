@@ -235,12 +235,40 @@ int32_t        kvq_scan_profile_cutoffs(const kvq_scan *s, uint8_t *cutoffs8);
 int32_t        kvq_profile_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
                                 const uint8_t *cutoffs, int32_t ncut, int64_t *out);
 
+/* ---- per-cycle quality and base composition: WHERE IN THE READ the profile's bytes stand ----
+ * The per-cycle counts cover exactly the records the profile covers; bases line and score line are as defined there, bytes are
+ * raw (a '\r' is a byte of its line).  CYCLE p of a record is byte p (0-based) of its bases line and, independently, byte p of
+ * its score line: each line has its own length (a record whose two lines differ in length is legal; the profile counts it in
+ * [3]).  Cycles 0 .. KVQ_CYCLES - 1 are counted (KVQ_CYCLES is the engine's KVQ_MAX_READLENGTH); bytes at positions of 1024 and
+ * beyond are counted nowhere in this array.  One flat int64 array of kvq_cycles_len() = 2 * 1024 * 256 words:
+ *   score[p][b]  at  p * 256 + b                 records whose score line has byte b at position p
+ *   base[p][b]   at  1024 * 256 + p * 256 + b    the same for the bases line
+ * Every word is a sum (no maxima).  With the profile of the same scan:
+ *   for every p < 1024:  sum_b base[p][b] == sum(raw_lengths[L] for L > p);
+ *   for every b:  sum_p score[p][b] <= score_bytes[b]  and  sum_p base[p][b] <= base_bytes[b], equalities when no line of that
+ *   kind has more than 1024 bytes (what lies beyond cycle 1023 is the difference);
+ *   sum_b score[0][b] is the number of records with a non-empty score line.
+ * kvq_scan_set_cycles: on != 0 turns the counts on, 0 off; before the first batch or after kvq_scan_reset (KVQ_ERR_RUNTIME
+ * otherwise).  They ride on the profile's record set and index: KVQ_ERR_RUNTIME when the scan keeps no profile, and
+ * kvq_scan_set_profile(..., ncut < 0) turns them off with it (so a scan with a communicator keeps none either).  Every batch
+ * is then counted once, right behind its profile pass; kvq_scan_finish brings the array to the host.  kvq_scan_cycles: the
+ * array (valid after kvq_scan_finish until the next reset), NULL when off.  The device array and its pinned landing buffer
+ * (4 MiB each) exist only while the option is on; with it off nothing is enqueued or allocated. */
+#define KVQ_CYCLES 1024
+int64_t        kvq_cycles_len(void);
+int32_t        kvq_scan_set_cycles(kvq_scan *s, int32_t on);
+const int64_t *kvq_scan_cycles(const kvq_scan *s);
+/* host only, plain C++: the CPU twin of kvq_profile_cycles over the same definition -- test infrastructure and the definition
+ * in running code, not a fallback.  Arguments as for kvq_profile_host; ADDS into out[0, kvq_cycles_len()). */
+int32_t        kvq_cycles_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t *out);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
 double  kvq_scan_kernel_ms(const kvq_scan *s);
 double  kvq_scan_main_kernel_ms(const kvq_scan *s);
 double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_profile_records alone (0 when the profile is off) */
+double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_profile_cycles alone (0 when the cycles are off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 int64_t kvq_scan_main_kernel_launches(const kvq_scan *s);
@@ -353,8 +381,11 @@ kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
 
 /* the same with the options as a structure (size: sizeof(kvq_find_opts), for later growth; flags: the KVQ_FIND_* above).
  * KVQ_FIND_PROFILE: the scan profiles its input at cutoffs[0, n_cutoffs) (kvq_scan_set_profile; kvq_scan_profile after the
- * call).  An empty sequence list is legal and gives a profile-only call.  opts == NULL: kvq_findseqs. */
+ * call).  An empty sequence list is legal and gives a profile-only call.  opts == NULL: kvq_findseqs.
+ * KVQ_FIND_CYCLES: the per-cycle counts too (kvq_scan_set_cycles; kvq_scan_cycles after the call); without KVQ_FIND_PROFILE it is
+ * KVQ_ERR_RUNTIME. */
 #define KVQ_FIND_PROFILE 8u
+#define KVQ_FIND_CYCLES 16u
 typedef struct kvq_find_opts {
     uint32_t size, flags;
     int32_t  n_cutoffs;

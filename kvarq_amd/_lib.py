@@ -13,6 +13,7 @@ CTR_RECORDS, CTR_LONGEST, CTR_HITS, CTR_READLENGTHS = 0, 1, 2, 4
 CELL_DENSE, CELL_DIAG, CELL_STAMPS = 0x1000, 0x2000, 0x4000      # kvq_scan_kernel_pick / kvq_scan_kernel
 FIND_RECORDS = 4                                                 # kvq_findseqs_ex: keep the records of the hits
 FIND_PROFILE = 8                                                 # kvq_findseqs_opts: profile the input
+FIND_CYCLES = 16                                                 # ... and count its bytes per cycle (with FIND_PROFILE)
 
 
 class Config(C.Structure):
@@ -101,9 +102,14 @@ PROTOTYPES = {
     'kvq_scan_profile': (P(i64), [vp]),
     'kvq_scan_profile_cutoffs': (i32, [vp, vp]),
     'kvq_profile_host': (i32, [vp, i64, P(i64), i64, vp, i32, P(i64)]),
+    'kvq_cycles_len': (i64, []),
+    'kvq_scan_set_cycles': (i32, [vp, i32]),
+    'kvq_scan_cycles': (P(i64), [vp]),
+    'kvq_cycles_host': (i32, [vp, i64, P(i64), i64, P(i64)]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),
+    'kvq_scan_cycles_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_gap_ms': (C.c_double, [vp, vp]),
     'kvq_scan_main_kernel_launches': (i64, [vp]),
     'kvq_scan_reset': (i32, [vp]),

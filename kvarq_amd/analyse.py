@@ -64,12 +64,13 @@ class Analyser(object):
 
     # -- scanning ------------------------------------------------------------------
 
-    def scan(self, fastq, templates, do_reverse=True, records=False, profile=None):
+    def scan(self, fastq, templates, do_reverse=True, records=False, profile=None, cycles=False):
         """``fastq``: a :class:`kvarq_amd.fastq.Fastq`; ``templates``: ordered mapping name -> plus-strand
         template (``Sequence``, text, or ``(text, left, right)``).  May raise ``FastqFileFormatException``.
         ``records=True`` keeps the FastQ record of every hit, gathered on the GPU during the scan, for
         :meth:`extract_hits`.  ``profile=<cutoffs>`` keeps the ``kvarq_amd.profile.Profile`` of the input in
-        ``self.profile`` (``encode`` then adds ``info['profile']``)."""
+        ``self.profile`` (``encode`` then adds ``info['profile']``); ``cycles=True`` takes the per-cycle counts into it
+        (``info['profile']['cycles']``)."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
         self.fastq_sizes = fastq.filesizes()
@@ -81,7 +82,7 @@ class Analyser(object):
         if do_reverse:
             seqs += [c.minus_seq.bases for c in self.coverages.values()]
         t0 = time.time()
-        ret = engine.findseqs(self.fastq_filenames, seqs, records=records, profile=profile)
+        ret = engine.findseqs(self.fastq_filenames, seqs, records=records, profile=profile, cycles=cycles)
         lo.debug('found %d hits' % len(ret['hits']))
         self.stats, self.hits, self.hitseqs = ret['stats'], ret['hits'], ret['hitseqs']
         self.records = ret.get('records')

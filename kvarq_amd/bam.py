@@ -198,11 +198,11 @@ class Bam(object):
     def Q2A(self, Q):
         return ASCII[Q + self.dQ]
 
-    def profile(self, cutoffs=None):
+    def profile(self, cutoffs=None, cycles=False):
         """a ``kvarq_amd.profile.Profile`` of the file's virtual FastQ text, taken on the GPU; cutoffs None: the
-        configured Amin"""
+        configured Amin; ``cycles``: with the per-cycle counts"""
         from . import profile as profile_
-        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs)
+        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs, cycles=cycles)
 
     def readrecordat(self, hit):
         raise IOError('the records of a BAM file are kept by the scan only: use Analyser.scan(..., records=True) '

@@ -212,3 +212,121 @@ kvq_profile_records(const uint8_t *__restrict__ data, const uint32_t *__restrict
     if (threadIdx.x < (uint32_t)ncut && sc[KvqProfLds::S_CUT_LONGEST + threadIdx.x])
         atomicMax(&prof[KVQ_PROF_CUTOFFS + threadIdx.x * KVQ_PROF_CUT_WORDS], (unsigned long long)sc[KvqProfLds::S_CUT_LONGEST + threadIdx.x]);
 }
+
+// ---- per-cycle counts (include/kvarq_hip.h) ----
+// How often every byte value stands at every position ("cycle") of the score lines and of the bases lines, positions
+// 0 .. KVQ_CYCLES - 1.  A LANE IS A POSITION: the 64 lanes of a wave hold 64 consecutive bytes of one line, so their 64 adds go
+// to 64 different LDS words on 32 different banks, whatever the bytes are (the byte histograms of kvq_profile_records queue
+// on a few words instead).  1024 x 256 bins do not fit LDS: the positions are cut into slabs of W (blockIdx.y), and a
+// workgroup keeps the HOT columns of its slab in LDS, 32-bit bins (a batch is < 4 GiB): score bytes '!' .. '~' and the bases
+// A C G T N.  Any other byte goes straight to the array with a 64-bit atomic: input made of cold bytes costs speed, never
+// results.
+#define KVQ_CYC_SCORE_LO 33u
+#define KVQ_CYC_SCORE_COLS 94u                                  // '!' .. '~'
+#define KVQ_CYC_COLS (KVQ_CYC_SCORE_COLS + 5u)                  // ... and A C G T N
+#define KVQ_CYC_SLAB 64u                                        // W; profiles/cycles_rate.txt has both widths, measured
+#define KVQ_CYC_SLAB_ALT 128u
+#define KVQ_CYC_RECORDS 4u                                      // records of a wave whose loads travel together
+
+// the LDS column of a byte of a bases line; -1: cold
+__device__ __forceinline__ int cyc_base_col(uint32_t b)
+{
+    return b == 'A' ? (int)KVQ_CYC_SCORE_COLS : b == 'C' ? (int)KVQ_CYC_SCORE_COLS + 1 : b == 'G' ? (int)KVQ_CYC_SCORE_COLS + 2
+         : b == 'T' ? (int)KVQ_CYC_SCORE_COLS + 3 : b == 'N' ? (int)KVQ_CYC_SCORE_COLS + 4 : -1;
+}
+
+// Grid: x over record shares (a wave takes 64 consecutive records at a time, a record index a lane; grid-stride), y over the
+// slabs slab0, slab0 + 1, ...  cyc: the array of include/kvarq_hip.h; behind it (cyc[kvq_cycles_len()]) one word of the
+// kernel's own: the longest line of either kind so far, a running maximum like KVQ_PROF_LONGEST but true for score lines too.
+// The launch of slab 0 raises it (every record reaches slab 0 or no slab); the launch of the other slabs, behind it on the
+// stream, reads it, and a workgroup whose slab no line reaches returns at once.  Static LDS: KVQ_CYC_COLS * W words, column
+// by column (word col * W + position: W is a multiple of 32, so the bank is the position's whatever the column).
+template <uint32_t W>
+__device__ __forceinline__ void cyc_slab(const uint8_t *__restrict__ data, const uint32_t *__restrict__ nl4, uint32_t nrec, uint32_t slab0,
+                                         unsigned long long *__restrict__ cyc)
+{
+    KVQ_BESIDE_SCAN();
+    __shared__ unsigned int bins[KVQ_CYC_COLS * W];
+    constexpr uint32_t NG = W / 64u;
+    constexpr size_t BASE = (size_t)KVQ_CYCLES * 256u, SCRATCH = 2u * BASE;
+    const uint32_t p0 = (slab0 + blockIdx.y) * W;
+    if (p0 >= KVQ_CYCLES) return;
+    if (p0 > 0u && (unsigned long long)p0 >= cyc[SCRATCH]) return;           // (the same for the whole workgroup)
+    for (uint32_t i = threadIdx.x; i < KVQ_CYC_COLS * W; i += blockDim.x) bins[i] = 0u;
+    __syncthreads();
+
+    const int lane = kvq_lane();
+    uint32_t longest = 0;
+    for (uint64_t g0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; g0 < nrec; g0 += (uint64_t)gridDim.x * 256u) {
+        // lane l: record g0 + l (behind the last record: two empty lines)
+        uint32_t boff = 0, L = 0, soff = 0, Q = 0;
+        if (g0 + (uint32_t)lane < nrec) {
+            uint32_t n[4];
+            __builtin_memcpy(n, nl4 + 4u * (size_t)(g0 + (uint32_t)lane), 16);
+            boff = n[0] + 1u; L = n[1] - n[0] - 1u; soff = n[2] + 1u; Q = n[3] - n[2] - 1u;
+        }
+        const uint32_t reach = L > Q ? L : Q;
+        longest = reach > longest ? reach : longest;
+        const unsigned long long todo = __ballot(reach > p0);
+        for (uint32_t r = 0; r < 64u; r += KVQ_CYC_RECORDS) {
+            if (!((todo >> r) & ((1ull << KVQ_CYC_RECORDS) - 1ull))) continue;
+            // the loads of KVQ_CYC_RECORDS records first, a byte a lane and never a byte that is not of the line; then their adds
+            uint32_t sb[KVQ_CYC_RECORDS][NG], bb[KVQ_CYC_RECORDS][NG], rL[KVQ_CYC_RECORDS], rQ[KVQ_CYC_RECORDS];
+#pragma unroll
+            for (uint32_t j = 0; j < KVQ_CYC_RECORDS; j++) {
+                const uint32_t ro = (uint32_t)__builtin_amdgcn_readlane((int)boff, (int)(r + j)), so = (uint32_t)__builtin_amdgcn_readlane((int)soff, (int)(r + j));
+                rL[j] = (uint32_t)__builtin_amdgcn_readlane((int)L, (int)(r + j)); rQ[j] = (uint32_t)__builtin_amdgcn_readlane((int)Q, (int)(r + j));
+#pragma unroll
+                for (uint32_t k = 0; k < NG; k++) {
+                    const uint32_t p = p0 + 64u * k + (uint32_t)lane;
+                    bb[j][k] = p < rL[j] ? data[(size_t)ro + p] : 0u;
+                    sb[j][k] = p < rQ[j] ? data[(size_t)so + p] : 0u;
+                }
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < KVQ_CYC_RECORDS; j++) {
+#pragma unroll
+                for (uint32_t k = 0; k < NG; k++) {
+                    const uint32_t at = 64u * k + (uint32_t)lane, p = p0 + at;
+                    if (p < rQ[j]) {
+                        const uint32_t col = sb[j][k] - KVQ_CYC_SCORE_LO;
+                        if (col < KVQ_CYC_SCORE_COLS) atomicAdd(&bins[col * W + at], 1u);
+                        else atomicAdd(&cyc[(size_t)p * 256u + sb[j][k]], 1ull);
+                    }
+                    if (p < rL[j]) {
+                        const int col = cyc_base_col(bb[j][k]);
+                        if (col >= 0) atomicAdd(&bins[(uint32_t)col * W + at], 1u);
+                        else atomicAdd(&cyc[BASE + (size_t)p * 256u + bb[j][k]], 1ull);
+                    }
+                }
+            }
+        }
+    }
+    if (p0 == 0u) {
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)longest, d, 64); longest = o > longest ? o : longest; }
+        if (lane == 0 && longest) atomicMax(&cyc[SCRATCH], (unsigned long long)longest);
+    }
+    __syncthreads();
+    // the workgroup's bins that are not zero -> the array; consecutive threads take consecutive bytes of one position, which
+    // are consecutive words of the array
+    for (uint32_t i = threadIdx.x; i < KVQ_CYC_COLS * W; i += blockDim.x) {
+        const uint32_t at = i / KVQ_CYC_COLS, col = i % KVQ_CYC_COLS;
+        const unsigned int v = bins[col * W + at];
+        if (!v) continue;
+        const size_t word = col < KVQ_CYC_SCORE_COLS ? (size_t)(p0 + at) * 256u + KVQ_CYC_SCORE_LO + col
+                                                     : BASE + (size_t)(p0 + at) * 256u + ((0x4E54474341ull >> (8u * (col - KVQ_CYC_SCORE_COLS))) & 0xFFu);      // "ACGTN"
+        atomicAdd(&cyc[word], (unsigned long long)v);
+    }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+kvq_profile_cycles(const uint8_t *__restrict__ data, const uint32_t *__restrict__ nl4, uint32_t nrec, uint32_t slab0, unsigned long long *__restrict__ cyc)
+{
+    cyc_slab<KVQ_CYC_SLAB>(data, nl4, nrec, slab0, cyc);
+}
+// (measurement, tools/cycles_rate.py: the other slab width)
+extern "C" __global__ void __launch_bounds__(256)
+kvq_profile_cycles_alt(const uint8_t *__restrict__ data, const uint32_t *__restrict__ nl4, uint32_t nrec, uint32_t slab0, unsigned long long *__restrict__ cyc)
+{
+    cyc_slab<KVQ_CYC_SLAB_ALT>(data, nl4, nrec, slab0, cyc);
+}

@@ -177,6 +177,10 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: at most %d cutoffs", KVQ_PROFILE_MAX_CUTOFFS);
         return nullptr;
     }
+    if ((flags & KVQ_FIND_CYCLES) && !(flags & KVQ_FIND_PROFILE)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_CYCLES needs KVQ_FIND_PROFILE (the cycles ride on the profile)");
+        return nullptr;
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -210,7 +214,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         s = t ? kvq_scan_create(t, nullptr) : nullptr;
     }
     if (s && (kvq_scan_set_records(s, (flags & KVQ_FIND_RECORDS) ? 1 : 0) ||
-              kvq_scan_set_profile(s, opts ? opts->cutoffs : nullptr, (flags & KVQ_FIND_PROFILE) ? opts->n_cutoffs : -1))) {
+              kvq_scan_set_profile(s, opts ? opts->cutoffs : nullptr, (flags & KVQ_FIND_PROFILE) ? opts->n_cutoffs : -1) ||
+              kvq_scan_set_cycles(s, (flags & KVQ_FIND_CYCLES) ? 1 : 0))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
     }
     const double tf1 = now_ms();
@@ -287,7 +292,7 @@ extern "C" kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
                                      const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, uint32_t flags)
 {
     kvq_find_opts o; memset(&o, 0, sizeof(o));
-    o.size = (uint32_t)sizeof(o); o.flags = flags & ~KVQ_FIND_PROFILE;       // (the profile has cutoffs: kvq_findseqs_opts)
+    o.size = (uint32_t)sizeof(o); o.flags = flags & ~(KVQ_FIND_PROFILE | KVQ_FIND_CYCLES);       // (the profile has cutoffs: kvq_findseqs_opts)
     return kvq_findseqs_opts(files, nfiles, seqs, seqlens, nseq, &o);
 }
 

@@ -185,8 +185,8 @@ struct kvq_scan {
     hipEvent_t ev_chain = nullptr;       // this scan's last seed-filter launch and its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles: what the next scan of the process waits for)
     int64_t parsed = 0, total = 0;
     // timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_prof, ev_free;     // ev_prof: around kvq_profile_records; ev_free: pairs of earlier scans, reused
-    double ms_all = 0, ms_main = 0, ms_prof = 0; int64_t main_launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_prof, ev_cyc, ev_free;     // ev_prof: around kvq_profile_records; ev_cyc: around kvq_profile_cycles; ev_free: pairs of earlier scans, reused
+    double ms_all = 0, ms_main = 0, ms_prof = 0, ms_cyc = 0; int64_t main_launches = 0;
     // results: ordered and laid out on the device (kernels_results.hip), one copy into pinned host memory
     DevBuf d_sort_tmp, d_sorted, d_result, d_order, d_finish;   // d_order: bucket arrays of the ordering; d_finish: KvqFinishState
     uint32_t order_nb_max = 0;                    // the bucket arrays in d_order are laid out for this many buckets
@@ -217,6 +217,11 @@ struct kvq_scan {
     bool profile_on = false; int32_t prof_ncut = 0; uint8_t prof_cuts[KVQ_PROFILE_MAX_CUTOFFS] = { 0 };
     DevBuf d_prof; int64_t *pin_prof = nullptr; size_t pin_prof_cap = 0;
     std::vector<int64_t> h_prof;
+    // the per-cycle counts beside it (kvq_scan_set_cycles): the same three, there only while the option is on; the device array
+    // has the kernel's own scratch word behind its kvq_cycles_len() words
+    bool cycles_on = false;
+    DevBuf d_cyc; int64_t *pin_cyc = nullptr; size_t pin_cyc_cap = 0;
+    std::vector<int64_t> h_cyc;
 };
 
 // kernels_seeded.hip

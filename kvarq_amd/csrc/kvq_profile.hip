@@ -9,6 +9,8 @@ extern "C" int64_t kvq_profile_len(int32_t ncut)
     return ncut < 0 || ncut > KVQ_PROFILE_MAX_CUTOFFS ? 0 : (int64_t)KVQ_PROF_CUTOFFS + (int64_t)ncut * KVQ_PROF_CUT_WORDS;
 }
 
+static void cycles_off(kvq_scan *s);
+
 extern "C" int32_t kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int32_t ncut)
 {
     kvq_clear_error();
@@ -16,7 +18,7 @@ extern "C" int32_t kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_profile: only before the first batch or after kvq_scan_reset");
         return KVQ_ERR_RUNTIME;
     }
-    if (ncut < 0) { s->profile_on = false; s->prof_ncut = 0; return KVQ_OK; }
+    if (ncut < 0) { s->profile_on = false; s->prof_ncut = 0; cycles_off(s); return KVQ_OK; }
     if (ncut > KVQ_PROFILE_MAX_CUTOFFS || (ncut > 0 && !cutoffs)) {
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_profile: at most %d cutoffs", KVQ_PROFILE_MAX_CUTOFFS);
         return KVQ_ERR_RUNTIME;
@@ -92,7 +94,104 @@ extern "C" int32_t kvq_scan_profile_cutoffs(const kvq_scan *s, uint8_t *cutoffs8
     return s->prof_ncut;
 }
 
-// ---- the twin ----
+// ---- per-cycle counts (include/kvarq_hip.h): the same four steps beside the profile's ----
+extern "C" int64_t kvq_cycles_len(void) { return 2 * (int64_t)KVQ_CYCLES * 256; }
+static size_t cycles_device_bytes() { return ((size_t)kvq_cycles_len() + 1) * 8; }       // (the kernel's scratch word behind the array)
+
+static void cycles_off(kvq_scan *s)
+{
+    if (s->d_cyc.p) (void)hipStreamSynchronize(s->stream);       // (a reset has enqueued its clearing: the block goes back to a cache other streams take from)
+    if (s->pin_cyc) pinned_give(s->pin_cyc, s->pin_cyc_cap);
+    s->pin_cyc = nullptr; s->pin_cyc_cap = 0;
+    s->d_cyc.release();
+    s->h_cyc.clear(); s->h_cyc.shrink_to_fit();
+    s->cycles_on = false;
+}
+
+static int cycles_clear(kvq_scan *s)
+{
+    KVQ_HIP(hipMemsetAsync(s->d_cyc.p, 0, cycles_device_bytes(), s->stream));
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_scan_set_cycles(kvq_scan *s, int32_t on)
+{
+    kvq_clear_error();
+    if (!s->batches.empty() || s->copied_pending || s->host_pending >= 0) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_cycles: only before the first batch or after kvq_scan_reset");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (!on) { cycles_off(s); return KVQ_OK; }
+    if (!s->profile_on) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_cycles: the scan keeps no profile (the cycles ride on its record set and index: kvq_scan_set_profile first)");
+        return KVQ_ERR_RUNTIME;
+    }
+    int rc;
+    if ((rc = s->d_cyc.ensure(cycles_device_bytes()))) return rc;
+    const size_t bytes = (size_t)kvq_cycles_len() * 8;
+    if (s->pin_cyc_cap < bytes) {
+        if (s->pin_cyc) pinned_give(s->pin_cyc, s->pin_cyc_cap);
+        s->pin_cyc = (int64_t *)pinned_take(bytes, &s->pin_cyc_cap);
+        if (!s->pin_cyc) { s->pin_cyc_cap = 0; s->d_cyc.release(); kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
+    }
+    s->cycles_on = true;
+    s->h_cyc.clear();
+    return cycles_clear(s);
+}
+
+// The slab width (kernels_profile.hip).  KVQ_CYCLES_SLAB=64 / 128: that width (tools/cycles_rate.py).
+static bool cycles_alt_width()
+{
+    static const char *e = getenv("KVQ_CYCLES_SLAB");
+    return e && (uint32_t)atoi(e) == KVQ_CYC_SLAB_ALT;
+}
+
+// the cycles pass over the R records of a batch, behind its profile pass: slab 0, which every record reaches and which raises
+// the longest line; then the other slabs, which read it (a workgroup of a slab that no line reaches returns at once)
+static int cycles_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    const bool alt = cycles_alt_width();
+    const uint32_t W = alt ? KVQ_CYC_SLAB_ALT : KVQ_CYC_SLAB;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 255) / 256, 1024);             // (the kernel strides over what there is)
+    auto *kernel = alt ? kvq_profile_cycles_alt : kvq_profile_cycles;
+    hipLaunchKernelGGL(kernel, dim3(grid, 1), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, 0u, s->d_cyc.as<unsigned long long>());
+    hipLaunchKernelGGL(kernel, dim3(grid, KVQ_CYCLES / W - 1u), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, 1u, s->d_cyc.as<unsigned long long>());
+    KVQ_HIP(hipGetLastError());
+    return KVQ_OK;
+}
+
+static int cycles_tail(kvq_scan *s)
+{
+    KVQ_HIP(hipMemcpyAsync(s->pin_cyc, s->d_cyc.p, (size_t)kvq_cycles_len() * 8, hipMemcpyDeviceToHost, s->stream));
+    return KVQ_OK;
+}
+static void cycles_landed(kvq_scan *s) { s->h_cyc.assign(s->pin_cyc, s->pin_cyc + kvq_cycles_len()); }
+
+extern "C" const int64_t *kvq_scan_cycles(const kvq_scan *s) { return s->cycles_on && s->finished && !s->h_cyc.empty() ? s->h_cyc.data() : nullptr; }
+
+// ---- the twins ----
+extern "C" int32_t kvq_cycles_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t *out)
+{
+    kvq_clear_error();
+    bool ok = out && nbytes >= 0 && nchunks >= 0 && (nchunks == 0 || chunk_off);
+    for (int64_t c = 0; ok && c <= nchunks && nchunks > 0; c++) ok = chunk_off[c] >= 0 && chunk_off[c] <= nbytes && (!c || chunk_off[c] >= chunk_off[c - 1]);
+    if (!ok) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_cycles_host: bad arguments"); return KVQ_ERR_RUNTIME; }
+    int64_t *const score = out, *const base = out + (int64_t)KVQ_CYCLES * 256;
+    for (int64_t c = 0; c < nchunks; c++) {
+        int64_t nl[4]; int have = 0;
+        for (int64_t i = chunk_off[c]; i < chunk_off[c + 1]; i++) {
+            if (text[i] != '\n') continue;
+            nl[have++] = i;
+            if (have < 4) continue;                                            // a complete record of the chunk
+            have = 0;
+            for (int64_t p = 0; p < KVQ_CYCLES && nl[0] + 1 + p < nl[1]; p++) base[p * 256 + text[nl[0] + 1 + p]]++;
+            for (int64_t p = 0; p < KVQ_CYCLES && nl[2] + 1 + p < nl[3]; p++) score[p * 256 + text[nl[2] + 1 + p]]++;
+        }
+    }
+    return KVQ_OK;
+}
+
 extern "C" int32_t kvq_profile_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
                                     const uint8_t *cutoffs, int32_t ncut, int64_t *out)
 {

@@ -112,7 +112,7 @@ PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
 PATH_DEVICE_BAM = 0x40                             # kvq_scan_path bit 6
 
 
-def findseqs(fname, sequences, *, inflate='host', records=False, profile=None):
+def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, cycles=False):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
@@ -145,7 +145,11 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None):
     ``kvarq_amd.profile.Profile`` of the whole input -- score and base bytes, read lengths,
     and what the quality trim leaves at each cutoff (characters, bytes or ints, at most 8;
     ``True``: the configured Amin alone) -- taken on the GPU during the scan (DESIGN
-    section 13).  ``sequences`` may then be empty."""
+    section 13).  ``sequences`` may then be empty.
+
+    cycles=True: that profile also holds the per-cycle counts -- how often every byte stands at
+    every position of the score and bases lines (``Profile.cycle_scores`` and what follows it;
+    DESIGN section 14).  Without ``profile`` it means a profile with no cutoffs."""
     import os, time
     global _last_inflate
     if inflate not in INFLATE_FLAGS:
@@ -186,10 +190,13 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None):
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
+    if cycles and profile is None:
+        profile = ()
     if profile is not None:
         from . import profile as profile_
         cuts = profile_.as_cutoffs(profile)
-        opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE,
+        opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE |
+                             (_lib.FIND_CYCLES if cycles else 0),
                              len(cuts), (C.c_uint8 * 8)(*cuts))
         h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opts))
     elif inflate == 'host' and not records:

@@ -2,14 +2,17 @@
 The profile of a whole input, taken on the GPU during the scan (include/kvarq_hip.h): which bytes
 the score and bases lines hold, how long the reads are, and what the engine's quality trim leaves of them at a few
 cutoffs -- the questions the reference answers from a sample of the file with ``kvarq show -Q q -i``
-(kvarq/cli.py:201-221) and in ``Fastq.__init__``, answered here for every record.
+(kvarq/cli.py:201-221) and in ``Fastq.__init__``, answered here for every record.  With ``cycles=True`` it also tells
+WHERE IN THE READ the bytes stand: a count per position ("cycle") and byte value of the score and of the bases lines
+(``Profile.cycle_scores`` and the methods behind it).
 
 ``profile(fnames, cutoffs)`` scans files with no sequences; ``engine.findseqs(..., profile=...)``,
 ``scan.Scanner(..., profile=...)``, ``Fastq.profile()``, ``Bam.profile()`` and ``Analyser.scan(..., profile=...)``
 take the profile along with a scan.  ``profile_host`` is the CPU twin of the kernel (the definition in running code
-and test infrastructure, not a fallback).  ``python -m kvarq_amd.profile FILE [-Q q ...]`` prints the summary.
+and test infrastructure, not a fallback).  ``python -m kvarq_amd.profile FILE [-Q q ...]`` prints the summary,
+``--cycles [--cycle-step N]`` a line per cycle (or per N cycles) behind it.
 
-Out of scope: per-cycle quality, profiles across ranks, and what ``Fastq`` guesses by default.
+Out of scope: profiles across ranks, and what ``Fastq`` guesses by default.
 """
 import ctypes as C
 
@@ -22,6 +25,10 @@ MAX_CUTOFFS = 8
 # the layout of the flat array (include/kvarq_hip.h)
 RECORDS, BASE_LINE_BYTES, SCORE_LINE_BYTES, MISMATCHED, LONGEST = 0, 1, 2, 3, 4
 SCORE_BYTES, BASE_BYTES, RAW_LENGTHS, RAW_BINS, CUTOFFS, CUT_WORDS = 8, 264, 520, 1025, 1545, 1025
+
+
+CYCLES = 1024                                   # KVQ_CYCLES
+CYCLES_LEN = 2 * CYCLES * 256                   # kvq_cycles_len(): score[p][b] at p * 256 + b, base[p][b] behind them
 
 
 def profile_len(ncut):
@@ -58,13 +65,51 @@ def _cut_array(cutoffs):
     return (C.c_uint8 * MAX_CUTOFFS)(*cutoffs)
 
 
+def _share(part, total):
+    """part / total, nan where total is 0"""
+    out = np.full(np.shape(part), np.nan)
+    np.divide(part, total, out=out, where=np.asarray(total) > 0)
+    return out
+
+
+def _without_cr(rows):
+    n = rows.copy()
+    n[:, 13] = 0
+    return n
+
+
+def _rows_mean_quality(rows, dQ):
+    n = _without_cr(rows)
+    return _share((n * (np.arange(256) - 33 - dQ)).sum(axis=1), n.sum(axis=1))
+
+
+def _rows_quantile(rows, q, dQ):
+    if not 0.0 <= q <= 1.0:
+        raise ValueError('a quantile lies in 0 .. 1')
+    cum = np.cumsum(_without_cr(rows), axis=1)
+    total = cum[:, -1]
+    byte = (cum >= np.maximum(q * total, 1)[:, None]).argmax(axis=1)          # (at least one score: q = 0 is the lowest score seen)
+    return np.where(total > 0, byte - 33.0 - dQ, np.nan)
+
+
+def _rows_base_share(rows):
+    acgtn = rows[:, [ord(c) for c in 'ACGTN']]
+    total = rows.sum(axis=1)
+    return _share(np.concatenate([acgtn, (total - acgtn.sum(axis=1))[:, None]], axis=1), total[:, None])
+
+
 class Profile(object):
     """a finished profile: ``records``, ``score_bytes`` / ``base_bytes`` (256 counts each), ``raw_lengths`` (1025 bins,
     the last one holding the lines of 1024 bytes and more), ``mismatched`` (records whose score and bases lines differ
-    in length), ``longest`` (the longest bases line, -1: none), ``cutoffs`` (byte values), ``words`` (the flat array)"""
+    in length), ``longest`` (the longest bases line, -1: none), ``cutoffs`` (byte values), ``words`` (the flat array);
+    ``cycles``: the flat per-cycle array (kvq_cycles_len() words) when the scan took it, else None"""
 
-    def __init__(self, words, cutoffs):
+    def __init__(self, words, cutoffs, cycles=None):
         self.cutoffs = list(cutoffs)
+        self.cycles = None
+        if cycles is not None:
+            self.cycles = np.array(cycles, dtype=np.int64)
+            assert self.cycles.shape == (CYCLES_LEN,)
         self.words = np.array(words, dtype=np.int64)
         assert self.words.shape == (profile_len(len(self.cutoffs)),)
         w = self.words
@@ -75,7 +120,11 @@ class Profile(object):
         self.raw_lengths = w[RAW_LENGTHS:RAW_LENGTHS + RAW_BINS]
 
     def __eq__(self, other):
-        return isinstance(other, Profile) and self.cutoffs == other.cutoffs and (self.words == other.words).all()
+        if not (isinstance(other, Profile) and self.cutoffs == other.cutoffs and (self.words == other.words).all()):
+            return False
+        if self.cycles is None or other.cycles is None:
+            return self.cycles is None and other.cycles is None
+        return bool((self.cycles == other.cycles).all())
 
     def __ne__(self, other):
         return not self == other
@@ -132,6 +181,79 @@ class Profile(object):
         dropped = int(bins[:max(int(minreadlength), 0)].sum())
         return (self.records - dropped) / float(self.records)
 
+    # -- per cycle ---------------------------------------------------------------
+
+    def _cycles(self):
+        if self.cycles is None:
+            raise ValueError('this profile was taken without cycles=True')
+        return self.cycles
+
+    @property
+    def cycle_scores(self):
+        """(1024, 256): records whose score line has byte b at position p"""
+        return self._cycles()[:CYCLES * 256].reshape(CYCLES, 256)
+
+    @property
+    def cycle_bases(self):
+        """(1024, 256): the same for the bases line"""
+        return self._cycles()[CYCLES * 256:].reshape(CYCLES, 256)
+
+    def cycles_reached(self, kind='score'):
+        """per cycle, the lines of that kind ('score' / 'base') that reach it"""
+        if kind not in ('score', 'base'):
+            raise ValueError("kind is 'score' or 'base'")
+        return (self.cycle_scores if kind == 'score' else self.cycle_bases).sum(axis=1)
+
+    @property
+    def last_cycle(self):
+        """the highest cycle any line reaches (-1: none)"""
+        reached = np.nonzero(self.cycles_reached('score') + self.cycles_reached('base'))[0]
+        return int(reached[-1]) if reached.size else -1
+
+    def cycle_mean_quality(self, dQ=None):
+        """per cycle, the mean PHRED score ('\\r' left out); nan where no record reaches the cycle"""
+        return _rows_mean_quality(self.cycle_scores, self.dQ() if dQ is None else dQ)
+
+    def cycle_quantile(self, q, dQ=None):
+        """per cycle, the lowest PHRED value whose cumulative count reaches ``q`` (0 .. 1) of the cycle's scores
+        ('\\r' left out); nan where no record reaches the cycle"""
+        return _rows_quantile(self.cycle_scores, q, self.dQ() if dQ is None else dQ)
+
+    def cycle_below(self, cutoff):
+        """per cycle, the share of its score bytes below ``cutoff``, compared as signed char as ``Amin`` is; nan where
+        no record reaches the cycle"""
+        c = as_cutoffs([cutoff])[0]
+        signed = np.arange(256) - 256 * (np.arange(256) >= 128)
+        n = self.cycle_scores
+        return _share(n[:, signed < (c - 256 if c >= 128 else c)].sum(axis=1), n.sum(axis=1))
+
+    def cycle_base_share(self):
+        """(1024, 6): per cycle the shares of A, C, G, T, N (upper case only) and of every other byte; nan where no
+        record reaches the cycle"""
+        return _rows_base_share(self.cycle_bases)
+
+    def cycle_lines(self, step=1, dQ=None):
+        """the per-cycle table of the command line, a line per ``step`` cycles up to ``last_cycle``: the score lines
+        reaching the (first) cycle, the mean Q, its 10 % / 50 % / 90 % quantiles, the shares of A C G T N"""
+        if dQ is None:
+            try:
+                dQ = self.dQ()
+            except FastqFileFormatException:
+                dQ = 0
+        step = max(int(step), 1)
+        starts = np.arange(0, self.last_cycle + 1, step)
+        lines = ['cycle reads meanQ Q10 Q50 Q90 A C G T N (dQ=%d)' % dQ]
+        if not starts.size:
+            return lines
+        scores, bases = np.add.reduceat(self.cycle_scores, starts, axis=0), np.add.reduceat(self.cycle_bases, starts, axis=0)
+        reached, mean, share = self.cycles_reached('score'), _rows_mean_quality(scores, dQ), _rows_base_share(bases)
+        quant = [_rows_quantile(scores, q, dQ) for q in (0.1, 0.5, 0.9)]
+        for i, a in enumerate(starts.tolist()):
+            b = min(a + step, CYCLES) - 1
+            lines.append('%s %d %.2f %s %s' % (a if b == a else '%d-%d' % (a, b), reached[a], mean[i], ' '.join('%g' % v[i] for v in quant),
+                                              ' '.join('%.3f' % v for v in share[i, :5])))
+        return lines
+
     def summary(self):
         lines = ['records=%d mismatched=%d longest=%d' % (self.records, self.mismatched, self.longest)]
         lo_, hi = self.score_range()
@@ -150,10 +272,15 @@ class Profile(object):
 
     def as_dict(self):
         """what ``Analyser.encode`` stores"""
-        return {'records': self.records, 'mismatched': self.mismatched, 'longest': self.longest,
-                'score_bytes': {int(b): int(self.score_bytes[b]) for b in np.nonzero(self.score_bytes)[0]},
-                'base_bytes': {int(b): int(self.base_bytes[b]) for b in np.nonzero(self.base_bytes)[0]},
-                'readlengths': {str(c): list(self.readlengths(c)) for c in self.cutoffs}}
+        d = {'records': self.records, 'mismatched': self.mismatched, 'longest': self.longest,
+             'score_bytes': {int(b): int(self.score_bytes[b]) for b in np.nonzero(self.score_bytes)[0]},
+             'base_bytes': {int(b): int(self.base_bytes[b]) for b in np.nonzero(self.base_bytes)[0]},
+             'readlengths': {str(c): list(self.readlengths(c)) for c in self.cutoffs}}
+        if self.cycles is not None:
+            def sparse(rows):
+                return [{int(b): int(row[b]) for b in np.nonzero(row)[0]} for row in rows[:self.last_cycle + 1]]
+            d['cycles'] = {'score': sparse(self.cycle_scores), 'base': sparse(self.cycle_bases)}
+        return d
 
 
 def from_scan(L, h):
@@ -163,11 +290,14 @@ def from_scan(L, h):
     ptr = L.kvq_scan_profile(h)
     if n < 0 or not ptr:
         return None
-    return Profile(np.ctypeslib.as_array(ptr, shape=(profile_len(n),)).copy(), list(cuts)[:n])
+    cyc = L.kvq_scan_cycles(h)
+    return Profile(np.ctypeslib.as_array(ptr, shape=(profile_len(n),)).copy(), list(cuts)[:n],
+                   np.ctypeslib.as_array(cyc, shape=(CYCLES_LEN,)).copy() if cyc else None)
 
 
-def profile_host(text, cutoffs=(), chunk_off=None):
-    """the CPU twin (kvq_profile_host) over a text in host memory; chunk_off None: the reader's chunk cuts"""
+def profile_host(text, cutoffs=(), chunk_off=None, cycles=False):
+    """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host) over a text in host memory; chunk_off None: the
+    reader's chunk cuts"""
     from . import scan
     cuts = as_cutoffs(cutoffs)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
@@ -177,13 +307,20 @@ def profile_host(text, cutoffs=(), chunk_off=None):
                                      len(co) - 1, _cut_array(cuts), len(cuts), out.ctypes.data_as(C.POINTER(C.c_int64)))
     if rc:
         raise RuntimeError(_lib.last_error()[1])
-    return Profile(out, cuts)
+    cyc = None
+    if cycles:
+        cyc = np.zeros(CYCLES_LEN, dtype=np.int64)
+        if _lib.lib().kvq_cycles_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      len(co) - 1, cyc.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError(_lib.last_error()[1])
+    return Profile(out, cuts, cyc)
 
 
-def profile(fnames, cutoffs=True, inflate='host'):
-    """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences"""
+def profile(fnames, cutoffs=True, inflate='host', cycles=False):
+    """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
+    per-cycle counts"""
     from . import engine
-    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs)['profile']
+    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, cycles=cycles)['profile']
 
 
 def main(argv=None):
@@ -193,12 +330,16 @@ def main(argv=None):
     ap.add_argument('files', nargs='+')
     ap.add_argument('-Q', '--quality', type=int, action='append', help='PHRED cutoff(s); default: the configured Amin')
     ap.add_argument('--inflate', default='host', choices=sorted(engine.INFLATE_FLAGS))
+    ap.add_argument('--cycles', action='store_true', help='a line per cycle: reads reaching it, mean Q, 10/50/90 %% quantiles, shares of A C G T N')
+    ap.add_argument('--cycle-step', type=int, default=1, metavar='N', help='a line per N cycles')
     a = ap.parse_args(argv)
-    p = profile(a.files, cutoffs=True, inflate=a.inflate)
+    p = profile(a.files, cutoffs=True, inflate=a.inflate, cycles=a.cycles and not a.quality)
     if a.quality:
         dQ = p.dQ()
-        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate)
+        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate, cycles=a.cycles)
     print(p.summary())
+    if a.cycles:
+        print('\n'.join(p.cycle_lines(a.cycle_step)))
 
 
 if __name__ == '__main__':

@@ -96,7 +96,7 @@ class Scanner(object):
     ``finish`` raises ``RescanRequired`` and the caller, who has the data, resets and feeds again; a caller with
     a re-readable source passes ``replay=callable`` (called with the scanner after ``reset()``) instead."""
 
-    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None):
+    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None, cycles=False):
         self.table = table
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
@@ -105,11 +105,16 @@ class Scanner(object):
         if self.records:
             _check(_lib.lib().kvq_scan_set_records(self.h, 1))
         # profile the input at these cutoffs (kvarq_amd.profile.as_cutoffs; True: the table's Amin); kept across reset
-        self.profile = None
+        # cycles: the per-cycle counts beside the profile (kvq_scan_set_cycles); without ``profile``: a profile with no cutoffs
+        self.profile, self.cycles = None, bool(cycles)
+        if self.cycles and profile is None:
+            profile = ()
         if profile is not None:
             from . import profile as profile_
             self.profile = profile_.as_cutoffs(profile, amin=bytes([table.config.Amin & 0xFF]))
             _check(_lib.lib().kvq_scan_set_profile(self.h, (C.c_uint8 * 8)(*self.profile), len(self.profile)))
+            if self.cycles:
+                _check(_lib.lib().kvq_scan_set_cycles(self.h, 1))
         self._host_batches = []          # copies of what scan_host was given since the last reset (fed again when the hit arena overflows)
         self._device_batches = []        # what scan_device was given since the last reset (the caller's device memory: nothing is copied)
         self._retained, self._retain_limit, self._replay = 0, (0 if replay is not None else retain_limit), replay
@@ -198,6 +203,8 @@ class Scanner(object):
             from . import profile as profile_
             out['profile'] = profile_.from_scan(L, self.h)
             out['profile_kernel_ms'] = L.kvq_scan_profile_kernel_ms(self.h)
+            if self.cycles:
+                out['cycles_kernel_ms'] = L.kvq_scan_cycles_kernel_ms(self.h)
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
