@@ -189,6 +189,17 @@ int64_t        kvq_scan_total(const kvq_scan *s);             /* fastq_size_esti
  * bytes of the distinct records held.  NULL / 0 when records are off. */
 int32_t        kvq_scan_set_records(kvq_scan *s, int32_t on);
 const uint8_t *kvq_scan_record_blob(const kvq_scan *s);
+/* ---- long reads: the read-list route ----
+ * A text of reads of thousands of bases (PacBio HiFi, nanopore) fits no tile of the seed-filter scan kernel and ends in the
+ * exhaustive kernels by default, which try every alignment.  kvq_scan_set_long_reads: mode 0 = off (the default), 1 = every
+ * batch takes the read-list route, 2 = auto: a batch takes it when the average record among its first 128 KiB
+ * (kvq_tile_for_text) is at least 2 * KVQ_MAX_READLENGTH + 25 bytes -- a read of 1024 bases -- or those hold too few lines
+ * for an average.  On the route a batch's records are indexed and trimmed as the exhaustive pass does it, the sequences
+ * without seeds go through the exhaustive matcher, and the seeded ones through the seed filter over the list of reads
+ * (kvq_seed_list): the same hits, counters and records, found by K-mer lookups instead of alignments.  Where the table has no
+ * seed index, or kvq_scan_force_exhaustive is on, a batch takes the ordinary path silently.  Before the first batch or after
+ * kvq_scan_reset (KVQ_ERR_RUNTIME otherwise); kept across kvq_scan_reset; allowed with a communicator. */
+int32_t        kvq_scan_set_long_reads(kvq_scan *s, int32_t mode);
 const int64_t *kvq_scan_hit_record_off(const kvq_scan *s);
 const int32_t *kvq_scan_hit_record_len(const kvq_scan *s);
 int64_t        kvq_scan_record_bytes(const kvq_scan *s);
@@ -280,7 +291,9 @@ int32_t kvq_scan_reset(kvq_scan *s);
  * bit 3 = tiles of the seed-filter pass left their records alone (a record longer than a tile's
  * look-ahead, more newlines than its tables hold) and those records were scanned again, bit 4 = the text was inflated
  * on the device (kvq_findseqs_ex, KVQ_FIND_DEVICE_INFLATE or KVQ_FIND_DEVICE_GZIP), bit 5 = a file of it took the speculative
- * route of KVQ_FIND_DEVICE_GZIP, bit 6 = the text was decoded from BAM on the device (kvq_findseqs on BAM files) */
+ * route of KVQ_FIND_DEVICE_GZIP, bit 6 = the text was decoded from BAM on the device (kvq_findseqs on BAM files),
+ * bit 7 = a batch took the read-list route (kvq_scan_set_long_reads): it sets bit 1 only when the exhaustive matcher ran for sequences
+ * without seeds, and never bit 0 */
 int32_t kvq_scan_path(const kvq_scan *s);
 /* 0 = let the table decide, 1 = force the exhaustive kernel for every sequence */
 void    kvq_scan_force_exhaustive(kvq_scan *s, int32_t on);
@@ -386,6 +399,10 @@ kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
  * KVQ_ERR_RUNTIME. */
 #define KVQ_FIND_PROFILE 8u
 #define KVQ_FIND_CYCLES 16u
+/* KVQ_FIND_LONG_READS / KVQ_FIND_LONG_READS_AUTO: kvq_scan_set_long_reads mode 1 / 2 for the call, whatever way the text
+ * takes to the GPU (host reader, device inflate, BAM). */
+#define KVQ_FIND_LONG_READS 32u
+#define KVQ_FIND_LONG_READS_AUTO 64u
 typedef struct kvq_find_opts {
     uint32_t size, flags;
     int32_t  n_cutoffs;

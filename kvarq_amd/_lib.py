@@ -14,6 +14,16 @@ CELL_DENSE, CELL_DIAG, CELL_STAMPS = 0x1000, 0x2000, 0x4000      # kvq_scan_kern
 FIND_RECORDS = 4                                                 # kvq_findseqs_ex: keep the records of the hits
 FIND_PROFILE = 8                                                 # kvq_findseqs_opts: profile the input
 FIND_CYCLES = 16                                                 # ... and count its bytes per cycle (with FIND_PROFILE)
+FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
+LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
+PATH_READ_LIST = 0x80                                            # kvq_scan_path bit 7
+
+
+def long_reads_mode(long_reads):
+    """the mode of kvq_scan_set_long_reads for a ``long_reads`` option (False, True or 'auto')"""
+    if not isinstance(long_reads, (bool, str)) or long_reads not in LONG_READS_MODES:
+        raise ValueError("long_reads must be False, True or 'auto'")
+    return LONG_READS_MODES[long_reads]
 
 
 class Config(C.Structure):
@@ -93,6 +103,7 @@ PROTOTYPES = {
     'kvq_scan_parsed': (i64, [vp]),
     'kvq_scan_total': (i64, [vp]),
     'kvq_scan_set_records': (i32, [vp, i32]),
+    'kvq_scan_set_long_reads': (i32, [vp, i32]),
     'kvq_scan_record_blob': (vp, [vp]),
     'kvq_scan_hit_record_off': (P(i64), [vp]),
     'kvq_scan_hit_record_len': (P(i32), [vp]),

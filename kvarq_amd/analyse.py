@@ -64,7 +64,7 @@ class Analyser(object):
 
     # -- scanning ------------------------------------------------------------------
 
-    def scan(self, fastq, templates, do_reverse=True, records=False, profile=None, cycles=False):
+    def scan(self, fastq, templates, do_reverse=True, records=False, profile=None, cycles=False, long_reads=False):
         """``fastq``: a :class:`kvarq_amd.fastq.Fastq`; ``templates``: ordered mapping name -> plus-strand
         template (``Sequence``, text, or ``(text, left, right)``).  May raise ``FastqFileFormatException``.
         ``records=True`` keeps the FastQ record of every hit, gathered on the GPU during the scan, for
@@ -82,7 +82,7 @@ class Analyser(object):
         if do_reverse:
             seqs += [c.minus_seq.bases for c in self.coverages.values()]
         t0 = time.time()
-        ret = engine.findseqs(self.fastq_filenames, seqs, records=records, profile=profile, cycles=cycles)
+        ret = engine.findseqs(self.fastq_filenames, seqs, records=records, profile=profile, cycles=cycles, long_reads=long_reads)
         lo.debug('found %d hits' % len(ret['hits']))
         self.stats, self.hits, self.hitseqs = ret['stats'], ret['hits'], ret['hitseqs']
         self.records = ret.get('records')

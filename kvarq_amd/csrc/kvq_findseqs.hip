@@ -214,6 +214,7 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         s = t ? kvq_scan_create(t, nullptr) : nullptr;
     }
     if (s && (kvq_scan_set_records(s, (flags & KVQ_FIND_RECORDS) ? 1 : 0) ||
+              kvq_scan_set_long_reads(s, (flags & KVQ_FIND_LONG_READS) ? 1 : (flags & KVQ_FIND_LONG_READS_AUTO) ? 2 : 0) ||
               kvq_scan_set_profile(s, opts ? opts->cutoffs : nullptr, (flags & KVQ_FIND_PROFILE) ? opts->n_cutoffs : -1) ||
               kvq_scan_set_cycles(s, (flags & KVQ_FIND_CYCLES) ? 1 : 0))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;

@@ -70,6 +70,7 @@ struct Batch {
     const uint8_t *d_data; int64_t nbytes; int64_t fpos_base;
     std::vector<int64_t> chunk_off;
     bool redone = false;      // its seed-filter pass failed validation; an exhaustive redo batch follows
+    int8_t read_list = -1;    // the batch takes the read-list route (run_batch decides once: a replayed batch goes the way it went); -1: not decided
     bool is_redo = false;     // this batch is such a redo (or the redo of another batch's skipped tiles)
     const uint8_t *staged = nullptr;   // device text owned by the caller while the batch is in flight (kvq_scan_staged): a host batch for every other purpose
 };
@@ -143,6 +144,7 @@ struct kvq_scan {
     kvq_comm *comm = nullptr;            // several GPUs: `finish` sums the counters of all ranks over it (kvq_dist.hip)
     hipStream_t stream = nullptr;
     bool force_exhaustive = false;
+    int long_mode = 0;                   // the read-list route (kvq_scan_set_long_reads): 0 off, 1 every batch, 2 the batches whose head says long reads
     // counters
     unsigned long long *d_ctr = nullptr; DevBuf d_ctr_own;
     std::vector<int64_t> h_ctr;

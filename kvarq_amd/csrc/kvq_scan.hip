@@ -266,6 +266,17 @@ extern "C" int32_t kvq_scan_set_records(kvq_scan *s, int32_t on)
     s->rec_store_bytes = 0;
     return s->records_on && !was ? records_prepare(s) : KVQ_OK;
 }
+extern "C" int32_t kvq_scan_set_long_reads(kvq_scan *s, int32_t mode)
+{
+    kvq_clear_error();
+    if (!s->batches.empty() || s->copied_pending || s->host_pending >= 0) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_long_reads: only before the first batch or after kvq_scan_reset");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (mode < 0 || mode > 2) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_long_reads: mode must be 0 (off), 1 (on) or 2 (auto)"); return KVQ_ERR_RUNTIME; }
+    s->long_mode = mode;
+    return KVQ_OK;
+}
 extern "C" int32_t kvq_scan_reset(kvq_scan *s)
 {
     kvq_clear_error();
@@ -309,6 +320,7 @@ static int new_event_pair(kvq_scan *s, std::vector<std::pair<hipEvent_t, hipEven
 // what the steps of run_batch share: the batch, how it is scanned, and its chunk table in the pool (chunk_table)
 struct BatchRun {
     const uint8_t *d_data; int64_t nbytes, nchunks, fpos_base; size_t batch_no;
+    bool read_list = false;          // the read-list route: the exhaustive pass's index and trim, then kvq_seed_list for the seeded sequences (no tiles, nothing staged)
     bool use_seeded;                 // the seed-filter kernel takes the sequences it serves; the exhaustive kernels the rest (else: all)
     KvqParams P;
     const uint32_t *d_co;            // the chunk offsets in the device half of the pool
@@ -401,7 +413,7 @@ static int exhaustive_pass(kvq_scan *s, BatchRun &B, const int32_t *d_exh, int32
                        B.fpos_base, (uint32_t)R, KvqDevCount{ nullptr, 0, 0, nullptr }, s->d_nl4.as<uint32_t>(), s->d_rec_start.as<uint32_t>(),
                        s->d_read_off.as<uint32_t>(), s->d_read_len.as<int32_t>(), hist_done ? 0 : 1, 16u, (unsigned int *)nullptr, 0u);
     if (n_exh > 0) {
-        const bool main_here = !B.use_seeded;
+        const bool main_here = !B.use_seeded && !B.read_list;     // (the read-list route's main kernel is kvq_seed_list)
         if (main_here) { if ((rc = new_event_pair(s, s->ev_main))) return rc; KVQ_HIP(hipEventRecord(s->ev_main.back().first, s->stream)); }
         hipLaunchKernelGGL(kvq_match_all, dim3((uint32_t)((R + 3) / 4)), dim3(256), 0, s->stream, B.P, d_data, B.fpos_base, (uint32_t)R, KvqDevCount{ nullptr, 0, 0, nullptr },
                            s->d_read_off.as<uint32_t>(), s->d_read_len.as<int32_t>(), d_exh, n_exh);
@@ -445,6 +457,31 @@ static void redo_skipped_tiles(kvq_scan *s, const BatchRun &B)
     }
 }
 
+// Does the batch take the read-list route (kvq_scan_set_long_reads)?  Only where it was asked for, the table has a seed index with seeded
+// sequences and nothing forces the exhaustive kernels; in auto mode only when the batch's head says long reads: the average record among its
+// first 128 KiB (kvq_tile_for_text) is at least a KVQ_LONG_READ read's (bases and scores of 1024 and the least the other two lines take) --
+// or the head holds too few lines for an average, which only lines of many KiB do.  The head is looked at with variables of its own: the
+// scan's tile geometry stays what its first batch made it.  Decided once per batch (a replayed batch goes the way it went).
+static int decide_read_list(kvq_scan *s, Batch &b, const uint8_t *d_data, bool exhaustive_only, bool *take)
+{
+    const kvq_table *t = s->t;
+    *take = false;
+    if (exhaustive_only || !s->long_mode || !t->index || t->seeded.empty() || s->force_exhaustive) return KVQ_OK;
+    if (b.read_list < 0) {
+        b.read_list = 1;
+        if (s->long_mode == 2) {
+            std::vector<uint8_t> head((size_t)std::min<int64_t>(b.nbytes, 128 << 10));
+            KVQ_HIP(hipMemcpyAsync(head.data(), d_data, head.size(), hipMemcpyDeviceToHost, s->stream));
+            KVQ_HIP(hipStreamSynchronize(s->stream));
+            uint32_t rec = 0;
+            (void)kvq_tile_for_text(head.data(), head.size(), &rec);
+            b.read_list = rec >= 2u * KVQ_MAX_READLENGTH + 25u || (rec == 0 && head.size() == (size_t)(128 << 10)) ? 1 : 0;
+        }
+    }
+    *take = b.read_list == 1;
+    return KVQ_OK;
+}
+
 // closing the batch: hits of this batch = arena[range[batch_no], range[batch_no + 1]) (kvq_commit_batch closes the range of a
 // seed-filter batch and merges or forgets what it staged); then the fold of its hits and, when asked for, their records
 static int close_batch(kvq_scan *s, const BatchRun &B)
@@ -469,17 +506,19 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
 {
     const kvq_table *t = s->t;
     const double tb0 = now_ms();
-    const Batch &b = s->batches[batch_no];         // (no step touches the list)
+    Batch &b = s->batches[batch_no];               // (no step touches the list)
     BatchRun B;
     B.d_data = d_data; B.nbytes = b.nbytes; B.nchunks = (int64_t)b.chunk_off.size() - 1; B.fpos_base = b.fpos_base; B.batch_no = batch_no;
     if (B.nbytes <= 0 || B.nchunks <= 0) return KVQ_OK;
     B.P = make_params(s);
-    B.use_seeded = t->index && !t->seeded.empty() && !s->force_exhaustive && !exhaustive_only;
-    s->cur_chunk_off = b.chunk_off;
-    const int32_t *d_exh = B.use_seeded ? t->d_exh.as<int32_t>() : t->d_all.as<int32_t>();
-    const int32_t n_exh = B.use_seeded ? (int32_t)t->exhaustive.size() : t->nseq;
-
     int rc;
+    if ((rc = decide_read_list(s, b, d_data, exhaustive_only, &B.read_list))) return rc;
+    B.use_seeded = t->index && !t->seeded.empty() && !s->force_exhaustive && !exhaustive_only && !B.read_list;
+    s->cur_chunk_off = b.chunk_off;
+    const bool split = B.use_seeded || B.read_list;        // the seeded sequences have a kernel of their own: the exhaustive kernels take the rest
+    const int32_t *d_exh = split ? t->d_exh.as<int32_t>() : t->d_all.as<int32_t>();
+    const int32_t n_exh = split ? (int32_t)t->exhaustive.size() : t->nseq;
+
     if ((rc = chunk_table(s, B, b.chunk_off.data()))) return rc;
     if ((rc = new_event_pair(s, s->ev_all))) return rc;
     KVQ_HIP(hipEventRecord(s->ev_all.back().first, s->stream));
@@ -493,6 +532,21 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
         s->main_launches++; s->path_bits |= 1;
     }
     if ((!B.use_seeded || n_exh > 0) && (rc = exhaustive_pass(s, B, d_exh, n_exh, B.use_seeded))) return rc;
+    if (B.read_list) {
+        // the reads the exhaustive pass has indexed and trimmed (and counted), through the seed filter for the seeded sequences: counters
+        // and err are written directly, as there -- nothing is speculated
+        s->path_bits |= 128;
+        if (B.nrec > 0) {
+            const SeedIndex *ix = t->index;
+            const uint32_t R = (uint32_t)B.nrec;
+            if ((rc = new_event_pair(s, s->ev_main))) return rc;
+            KVQ_HIP(hipEventRecord(s->ev_main.back().first, s->stream));
+            hipLaunchKernelGGL(kvq_seed_list, dim3(std::min<uint32_t>((R + 3u) / 4u, KVQ_LIST_GRID_MAX)), dim3(256), 0, s->stream, B.P, d_data, B.fpos_base, R,
+                               s->d_read_off.as<uint32_t>(), s->d_read_len.as<int32_t>(), t->d_seeded.as<int32_t>(), (int32_t)t->seeded.size(), ix->dev, (int32_t)ix->k);
+            KVQ_HIP(hipEventRecord(s->ev_main.back().second, s->stream));
+            s->main_launches++;
+        }
+    }
     if (B.use_seeded && s->cur_ntiles) redo_skipped_tiles(s, B);      // (a batch of empty chunks has scanned no tile: nothing was skipped, and the redo's counts are the LAST launch's)
     if ((rc = close_batch(s, B))) return rc;
     // the profile: every batch once, by its first pass (the redo of a batch that failed validation leaves it alone, and so does

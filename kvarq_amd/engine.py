@@ -106,13 +106,14 @@ def _stats_dict(readlengths, longest, nseqbasehits, nseqhits, parsed, total, sig
 
 
 _last_inflate = None
+_last_long_reads = None
 INFLATE_FLAGS = {'host': 0, 'device': 1, 'device_any': 2}     # KVQ_FIND_DEVICE_INFLATE, KVQ_FIND_DEVICE_GZIP
 PATH_DEVICE_INFLATE = 0x10                         # kvq_scan_path bit 4
 PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
 PATH_DEVICE_BAM = 0x40                             # kvq_scan_path bit 6
 
 
-def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, cycles=False):
+def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, cycles=False, long_reads=False):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
@@ -149,12 +150,20 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
 
     cycles=True: that profile also holds the per-cycle counts -- how often every byte stands at
     every position of the score and bases lines (``Profile.cycle_scores`` and what follows it;
-    DESIGN section 14).  Without ``profile`` it means a profile with no cutoffs."""
+    DESIGN section 14).  Without ``profile`` it means a profile with no cutoffs.
+
+    long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
+    15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
+    no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are
+    found by K-mer lookups over the list of trimmed reads.  The results are the same.  'auto': only the
+    batches whose first records average a read of 1024 bases or more take it.  With a sequence list that
+    has no seed index the option changes nothing.  last_long_reads() tells whether the route ran."""
     import os, time
-    global _last_inflate
+    global _last_inflate, _last_long_reads
+    long_flag = (0, _lib.FIND_LONG_READS, _lib.FIND_LONG_READS_AUTO)[_lib.long_reads_mode(long_reads)]
     if inflate not in INFLATE_FLAGS:
         raise ValueError("inflate must be 'host', 'device' or 'device_any'")
-    _last_inflate = None
+    _last_inflate = _last_long_reads = None
     t_in = time.perf_counter()
     L = _lib.lib()
     if isinstance(fname, (str, bytes)):
@@ -195,20 +204,21 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
     if profile is not None:
         from . import profile as profile_
         cuts = profile_.as_cutoffs(profile)
-        opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE |
+        opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | long_flag | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE |
                              (_lib.FIND_CYCLES if cycles else 0),
                              len(cuts), (C.c_uint8 * 8)(*cuts))
         h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opts))
-    elif inflate == 'host' and not records:
+    elif inflate == 'host' and not records and not long_flag:
         h = L.kvq_findseqs(farr, len(bfiles), sarr, lens, n)
     else:
-        h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate] | (_lib.FIND_RECORDS if records else 0))
+        h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate] | long_flag | (_lib.FIND_RECORDS if records else 0))
     t_1 = time.perf_counter()
     try:
         if h:
             path = L.kvq_scan_path(h)
             _last_inflate = ('device_bam' if path & PATH_DEVICE_BAM else 'device_gzip' if path & PATH_DEVICE_GZIP
                              else 'device' if path & PATH_DEVICE_INFLATE else 'host')
+            _last_long_reads = bool(path & _lib.PATH_READ_LIST)
         code, _ = _lib.last_error()
         if not h or code:
             _raise_last()
@@ -274,6 +284,11 @@ def last_inflate():
     'device_bam' (BAM files, decoded to FastQ text on the GPU), 'host' (the reader on the CPU,
     plain files included), or None before any call"""
     return _last_inflate
+
+
+def last_long_reads():
+    """whether a batch of the last findseqs call took the read-list route (``long_reads``); None before any call"""
+    return _last_long_reads
 
 
 def last_bam_report():

@@ -316,11 +316,11 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False):
     return Profile(out, cuts, cyc)
 
 
-def profile(fnames, cutoffs=True, inflate='host', cycles=False):
+def profile(fnames, cutoffs=True, inflate='host', cycles=False, long_reads=False):
     """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
     per-cycle counts"""
     from . import engine
-    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, cycles=cycles)['profile']
+    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, cycles=cycles, long_reads=long_reads)['profile']
 
 
 def main(argv=None):

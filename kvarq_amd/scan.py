@@ -96,8 +96,9 @@ class Scanner(object):
     ``finish`` raises ``RescanRequired`` and the caller, who has the data, resets and feeds again; a caller with
     a re-readable source passes ``replay=callable`` (called with the scanner after ``reset()``) instead."""
 
-    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None, cycles=False):
+    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None, cycles=False, long_reads=False):
         self.table = table
+        long_mode = _lib.long_reads_mode(long_reads)
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
@@ -115,6 +116,10 @@ class Scanner(object):
             _check(_lib.lib().kvq_scan_set_profile(self.h, (C.c_uint8 * 8)(*self.profile), len(self.profile)))
             if self.cycles:
                 _check(_lib.lib().kvq_scan_set_cycles(self.h, 1))
+        # the read-list route for reads of thousands of bases (kvq_scan_set_long_reads; True, or 'auto': by each batch's head); kept across reset
+        self.long_reads = long_reads
+        if long_mode:
+            _check(_lib.lib().kvq_scan_set_long_reads(self.h, long_mode))
         self._host_batches = []          # copies of what scan_host was given since the last reset (fed again when the hit arena overflows)
         self._device_batches = []        # what scan_device was given since the last reset (the caller's device memory: nothing is copied)
         self._retained, self._retain_limit, self._replay = 0, (0 if replay is not None else retain_limit), replay
@@ -224,6 +229,8 @@ class Scanner(object):
         out['mutations'] = ctr[t.off_mutations:t.off_mutations + 6 * t.bases]
         path = L.kvq_scan_path(self.h)
         out['path'] = {'seeded': bool(path & 1), 'exhaustive': bool(path & 2), 'rescanned': bool(path & 4), 'tiles_rescanned': bool(path & 8)}
+        if self.long_reads is not False:
+            out['path']['read_list'] = bool(path & _lib.PATH_READ_LIST)      # a batch took the read-list route
         out['kernel'] = _lib.kernel_cell(L.kvq_scan_kernel(self.h))      # the scan kernel instantiation of the last seed-filter launch
         out['grid'] = L.kvq_scan_grid(self.h)                            # ... and its workgroups (0: no such launch)
         return out
