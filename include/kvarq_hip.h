@@ -282,6 +282,18 @@ double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_prof
 double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_profile_cycles alone (0 when the cycles are off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
+/* (measurement) how kvq_scan_finish put the hits of the finished scan in order:
+ *   out[0] n       hits put in order            out[5] crowded  a bucket held more than 64 hits
+ *   out[1] nb      buckets of the ordering      out[6] 1 when the merge sort produced the result (a crowded
+ *   out[2] shift   bucket = (file_pos - lo) >> shift            bucket, or KVQ_ORDER=mergesort), 0: the bucket ordering
+ *   out[3] bc      buckets per ordering workgroup (512 contiguous shares)
+ *   out[4] lo      smallest fpos_base of the scan's batches
+ *   out[7], out[8] hits the arena and bytes the hit blob hold NOW (grown by an overflow; valid at any time).
+ * out[0..6] are zero until the scan is finished.  The tests assert with it that an input reached the seam it was built for.
+ * Environment, read when a scan object is created: KVQ_ARENA_CAP=<hits> and KVQ_BLOB_CAP=<bytes> shrink the first
+ * arena (2^20 hits) and hit blob (64 MiB), to no less than 64 hits / 256 bytes; growth after an overflow is unchanged.
+ * Read at every finish: KVQ_ORDER=mergesort orders every scan with the comparison sort. */
+void    kvq_scan_order_info(const kvq_scan *s, int64_t out[9]);
 int64_t kvq_scan_main_kernel_launches(const kvq_scan *s);
 /* forget accumulated hits/counters/timers but keep buffers (bench steps) */
 int32_t kvq_scan_reset(kvq_scan *s);

@@ -108,8 +108,9 @@ static int records_fetch(kvq_scan *s, uint64_t n_hits, unsigned long long used)
     return KVQ_OK;
 }
 
-// KVQ_ORDER=mergesort: the comparison sort for every scan, not only for crowded buckets
-static bool order_by_mergesort() { static const bool on = getenv("KVQ_ORDER") && !strcmp(getenv("KVQ_ORDER"), "mergesort"); return on; }
+// KVQ_ORDER=mergesort: the comparison sort for every scan, not only for crowded buckets.  Asked once per tail (enqueue_tail), so
+// that a process can switch between the two orderings from one finish to the next; finish_once goes by what its tail was given
+static bool order_by_mergesort() { const char *e = getenv("KVQ_ORDER"); return e && !strcmp(e, "mergesort"); }
 
 static int enqueue_tail(kvq_scan *s)
 {
@@ -142,7 +143,8 @@ static int enqueue_tail(kvq_scan *s)
                        (long long)lo, (long long)hi, nb_max, d_st);
     if (t->nseq > 0)
         hipLaunchKernelGGL(kvq_cov_apply, dim3((uint32_t)((t->nseq + 3) / 4)), dim3(256), 0, s->stream, make_params(s));
-    if (!order_by_mergesort() &&
+    s->tail_mergesort = order_by_mergesort();
+    if (!s->tail_mergesort &&
         (rc = kvq_order_by_buckets(s->stream, s->d_arena.as<KvqHit>(), s->d_blob.as<uint8_t>(), s->blob_cap, d_st, W, s->d_result.as<uint8_t>()))) return rc;
     if (s->records_on && (rc = records_tail(s, d_st))) return rc;
     if (s->profile_on && (rc = profile_tail(s))) return rc;
@@ -267,7 +269,8 @@ static int finish_once(kvq_scan *s)
             spec = 0;
         }
         bool refetch = L.total > spec;
-        if (n_hits && (order_by_mergesort() || st.crowded)) {
+        const bool by_mergesort = n_hits && (s->tail_mergesort || st.crowded);
+        if (by_mergesort) {
             // crowded buckets (or the comparison sort asked for): order the hits with the merge sort instead
             if ((rc = kvq_order_by_mergesort(s->stream, s->d_arena.as<KvqHit>(), n_hits, s->d_blob.as<uint8_t>(), s->blob_cap, d_st,
                                              s->d_sort_tmp, s->d_sorted, s->d_result.as<uint8_t>()))) return rc;
@@ -286,6 +289,8 @@ static int finish_once(kvq_scan *s)
         s->pin_res = s->pin + ctr_b;
         if (!n_hits) memset(s->pin_res + L.hitseq_off, 0, 8);
         s->res = L; s->n_hits = n_hits;
+        { const int64_t info[7] = { (int64_t)st.n, (int64_t)st.nb, (int64_t)st.shift, (int64_t)st.bc, (int64_t)st.lo, (int64_t)st.crowded, by_mergesort ? 1 : 0 };
+          memcpy(s->order_info, info, sizeof(info)); }
         s->spec_bytes = L.total + L.total / 8 + 65536;
         sum_timing(s);
         s->finished = true;
@@ -405,5 +410,11 @@ extern "C" double kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b)
     float ms = 0;
     if (hipEventElapsedTime(&ms, a->ev_main.back().second, b->ev_main.front().first) != hipSuccess) { (void)hipGetLastError(); return -1.0; }
     return (double)ms;
+}
+// (measurement) how the finished scan's hits were put in order: what kvq_finish_plan left, and the capacities as they are now
+extern "C" void kvq_scan_order_info(const kvq_scan *s, int64_t out[9])
+{
+    for (int i = 0; i < 7; i++) out[i] = s->finished ? s->order_info[i] : 0;
+    out[7] = (int64_t)s->arena_cap; out[8] = (int64_t)s->blob_cap;
 }
 extern "C" int64_t kvq_scan_main_kernel_launches(const kvq_scan *s) { return s->main_launches; }

@@ -128,7 +128,14 @@ static int scan_init(kvq_scan *s, void *d_counters)
     const KvqSmall small(s->d_small.p);
     s->d_arena_n = small.arena_n; s->d_blob_n = small.blob_n; s->d_err = small.err; s->d_err_stage = small.err_stage;
     s->d_range = small.range; s->d_fail = small.fail; s->d_stage_ctr = small.stage_ctr;
-    if ((rc = ensure_arena(s, 1u << 20, 64ull << 20))) return rc;
+    {
+        // KVQ_ARENA_CAP=<hits>, KVQ_BLOB_CAP=<bytes>: a smaller first arena / blob (the tests reach "exactly full", "one more" and the
+        // grow-and-rescan paths at small shapes with them); never larger than the defaults, never below 64 hits / 256 bytes
+        unsigned long long hits = 1u << 20, blob = 64ull << 20;
+        if (const char *e = getenv("KVQ_ARENA_CAP")) { const long long v = atoll(e); if (v >= 0 && (unsigned long long)v < hits) hits = std::max<unsigned long long>((unsigned long long)v, 64); }
+        if (const char *e = getenv("KVQ_BLOB_CAP")) { const long long v = atoll(e); if (v >= 0 && (unsigned long long)v < blob) blob = std::max<unsigned long long>((unsigned long long)v, 256); }
+        if ((rc = ensure_arena(s, hits, blob))) return rc;
+    }
     if ((rc = s->d_surv.ensure(KvqSurvivors::bytes()))) return rc;
     {
         // header: slots handed out, the list's size (KVQ_SURV_CAP=<slots> shrinks it for the tests: a full list costs speed, never results)

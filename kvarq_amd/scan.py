@@ -235,6 +235,15 @@ class Scanner(object):
         out['grid'] = L.kvq_scan_grid(self.h)                            # ... and its workgroups (0: no such launch)
         return out
 
+    ORDER_INFO = ('n', 'nb', 'shift', 'bc', 'lo', 'crowded', 'mergesort', 'arena_cap', 'blob_cap')
+
+    def order_info(self):
+        """(measurement) ``kvq_scan_order_info``: how the finished scan's hits were put in order, and the capacities of
+        the hit arena and the hit blob as they are now"""
+        out = (C.c_int64 * 9)()
+        _lib.lib().kvq_scan_order_info(self.h, out)
+        return dict(zip(self.ORDER_INFO, (int(x) for x in out)))
+
     def hit_arrays(self):
         """the library's result arrays as numpy arrays (copies): seq_nr, file_pos, seq_pos, length, readlength,
         hitseq offsets (n + 1), hit bytes"""
