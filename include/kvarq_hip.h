@@ -294,6 +294,16 @@ double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
  * arena (2^20 hits) and hit blob (64 MiB), to no less than 64 hits / 256 bytes; growth after an overflow is unchanged.
  * Read at every finish: KVQ_ORDER=mergesort orders every scan with the comparison sort. */
 void    kvq_scan_order_info(const kvq_scan *s, int64_t out[9]);
+/* (measurement) which matchers the last seed-filter launch of the finished scan handed its work to:
+ *   out[0] slots of the survivors' list handed out (kvq_verify_survivors counts their bytes; the slots come sixteen at a
+ *          time, so this is no count of work items, and it passes out[1] when the list ran full)
+ *   out[1] slots the list has (2^22, or what KVQ_SURV_CAP=<slots>, read when the scan object is created, cut it to;
+ *          0: every work item is verified where it was found, bp_verify_rest); valid at any time
+ *   out[2] records the launch's skipped tiles left on the redo's list (kvq_match_all)
+ *   out[3] the reads of 1024 bases and more among them, on a list of their own (kvq_match_long)
+ * out[0], out[2], out[3] are zero until the scan is finished and when it had no seed-filter launch.  The words are read
+ * from the device when this is called; a scan that does not call it does nothing for it.  Returns 0 or an error code. */
+int32_t kvq_scan_match_info(const kvq_scan *s, int64_t out[4]);
 int64_t kvq_scan_main_kernel_launches(const kvq_scan *s);
 /* forget accumulated hits/counters/timers but keep buffers (bench steps) */
 int32_t kvq_scan_reset(kvq_scan *s);

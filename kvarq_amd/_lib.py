@@ -123,6 +123,7 @@ PROTOTYPES = {
     'kvq_scan_cycles_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_gap_ms': (C.c_double, [vp, vp]),
     'kvq_scan_order_info': (None, [vp, P(i64)]),
+    'kvq_scan_match_info': (i32, [vp, P(i64)]),
     'kvq_scan_main_kernel_launches': (i64, [vp]),
     'kvq_scan_reset': (i32, [vp]),
     'kvq_scan_path': (i32, [vp]),

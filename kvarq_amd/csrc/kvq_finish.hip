@@ -417,4 +417,16 @@ extern "C" void kvq_scan_order_info(const kvq_scan *s, int64_t out[9])
     for (int i = 0; i < 7; i++) out[i] = s->finished ? s->order_info[i] : 0;
     out[7] = (int64_t)s->arena_cap; out[8] = (int64_t)s->blob_cap;
 }
+// (measurement) the lists the finished scan's last seed-filter launch left behind: the words are read from the device here, when asked
+// (kvq_expand_tiles zeroes the three counts in front of every such launch; nothing on the scan's path looks at them for this)
+extern "C" int32_t kvq_scan_match_info(const kvq_scan *s, int64_t out[4])
+{
+    out[0] = out[2] = out[3] = 0; out[1] = (int64_t)s->surv_cap;
+    if (!s->finished || !s->kernel_cell) return KVQ_OK;
+    unsigned int sv = 0, rd[2] = { 0, 0 };
+    if (s->d_surv.p) KVQ_HIP(hipMemcpy(&sv, KvqSurvivors(s->d_surv.p).count, 4, hipMemcpyDeviceToHost));
+    if (s->d_redo.p) KVQ_HIP(hipMemcpy(rd, KvqRedo(s->d_redo.p).count, 8, hipMemcpyDeviceToHost));
+    out[0] = sv; out[2] = rd[0]; out[3] = rd[1];
+    return KVQ_OK;
+}
 extern "C" int64_t kvq_scan_main_kernel_launches(const kvq_scan *s) { return s->main_launches; }

@@ -244,6 +244,15 @@ class Scanner(object):
         _lib.lib().kvq_scan_order_info(self.h, out)
         return dict(zip(self.ORDER_INFO, (int(x) for x in out)))
 
+    MATCH_INFO = ('survivors', 'survivors_cap', 'redo_records', 'redo_long')
+
+    def match_info(self):
+        """(measurement) ``kvq_scan_match_info``: the survivors' slots the finished scan's last seed-filter launch handed
+        out, the slots its list has, the records its skipped tiles left to the redo and the long reads among them"""
+        out = (C.c_int64 * 4)()
+        _check(_lib.lib().kvq_scan_match_info(self.h, out))
+        return dict(zip(self.MATCH_INFO, (int(x) for x in out)))
+
     def hit_arrays(self):
         """the library's result arrays as numpy arrays (copies): seq_nr, file_pos, seq_pos, length, readlength,
         hitseq offsets (n + 1), hit bytes"""
