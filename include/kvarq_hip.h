@@ -273,6 +273,66 @@ const int64_t *kvq_scan_cycles(const kvq_scan *s);
  * in running code, not a fallback.  Arguments as for kvq_profile_host; ADDS into out[0, kvq_cycles_len()). */
 int32_t        kvq_cycles_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t *out);
 
+/* ---- per-read GC, mean quality, N counts and duplication: WHAT THE INDIVIDUAL READS LOOK LIKE ----
+ * Record set, bases line and score line are the profile's, with one difference: for everything below A TRAILING '\r' IS NOT
+ * PART OF ITS LINE (a mean or a key with a '\r' in it is of no use).
+ * The per-read distributions: one flat int64 array of kvq_reads_len() = 8 + 101 + 256 + 256 words, every word a sum:
+ *   [0] records counted      [1] gc_none: records whose bases line holds no A C G T      [2] meanq_none: records with an
+ *   empty score line         [3..7] 0
+ *   [8 .. +101)    gc[k]: with a the bytes of the bases line in {A,C,G,T} and g those in {G,C} (upper case only), a record with
+ *                  a > 0 counts in bin k = (200 g + a) / (2 a) -- integer division: the GC share in per cent, round half up
+ *   [109 .. +256)  meanq[b]: with n the bytes of the score line and S their sum as unsigned bytes, a record with n > 0 counts in
+ *                  bin b = (2 S + n) / (2 n): the mean score byte, round half up
+ *   [365 .. +256)  ncount[min(c, 255)], c the 'N' bytes of the bases line
+ * Lines may be of any length.  [0] == [1] + sum(gc) == [2] + sum(meanq) == sum(ncount) == the profile's records.
+ * The duplication: a record's KEY is the first n = min(L, 64) bytes of its bases line of L bytes; a record with L == 0 has none
+ * ("unkeyed").  Two records are duplicates when the 64-bit hashes of their keys are equal:
+ *   key zero-padded to 64 bytes, as eight little-endian 64-bit words w0..w7;  G = 0x9E3779B97F4A7C15
+ *   m(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *   h = m(n + G);  for i in 0..7: h ^= m(w_i + (i + 1) * G);  h = m(h);  if (h == 0) h = 1
+ * (kvq_dup_hash in kvarq_amd/csrc/kvq_dup_hash.h: one __host__ __device__ function for the kernel and the CPU twin.)
+ * The keys are counted in a hash table of C slots {hash, count}, C a power of two, the slot from the HIGH bits of h.  Key h is
+ * TRACKED AT LEVEL s when its s LOW bits are zero.  The result is defined without reference to batches or launches: the LEVEL
+ * is the smallest s for which the whole input holds at most C / 2 distinct tracked keys, and the table then holds exactly those
+ * keys, each with its full count.  At level 0 that is the exact duplication of the input; above, the exact duplication of a
+ * deterministic 1 / 2^s sample of the DISTINCT SEQUENCES, unbiased for the level histogram (FastQC's "first 100 000 sequences"
+ * is neither, and a GPU cannot reproduce it run to run).  The result array, kvq_dup_len() = 8 + 16 + 16 words:
+ *   [0] level     [1] C     [2] keyed records     [3] unkeyed records     [4] tracked records (the sum of the counts)
+ *   [5] tracked distinct keys     [6..7] 0
+ *   [8 .. +16) distinct[], [24 .. +16) records[]: the tracked keys, and their records, by the key's count, in bins with the
+ *   lower bounds 1 2 3 4 5 6 7 8 9 10 50 100 500 1000 5000 10000
+ *   [2] + [3] == the profile's records, sum(records[]) == [4], sum(distinct[]) == [5], at level 0 [4] == [2].
+ * C is 2^24 (two tables: 512 MB of device memory, there only while the option is on): a choice, not a measurement.
+ * KVQ_DUP_SLOTS=<n> in the environment, read when the option is turned on, shrinks it, to no less than 1024, rounded down to a
+ * power of two (the tests reach levels above 0 with a few thousand records that way).
+ * kvq_scan_set_read_stats: mode bit 0 the distributions, bit 1 the duplication, 0 both off; before the first batch or after
+ * kvq_scan_reset (KVQ_ERR_RUNTIME otherwise).  They ride on the profile's record set and index as the cycles do: KVQ_ERR_RUNTIME
+ * when the scan keeps no profile, off together with it, none with a communicator.  Every batch is then counted once, behind its
+ * profile (and cycles) pass; wherever the profile is cleared the arrays AND THE TABLE are.  kvq_scan_reads / kvq_scan_dup: the
+ * arrays (valid after kvq_scan_finish until the next reset), NULL when that option is off.  Device memory and landing buffers
+ * exist only while an option is on; with both off nothing is enqueued or allocated. */
+enum { KVQ_READS_RECORDS = 0, KVQ_READS_GC_NONE = 1, KVQ_READS_MEANQ_NONE = 2, KVQ_READS_GC = 8, KVQ_READS_GC_BINS = 101,
+       KVQ_READS_MEANQ = 109, KVQ_READS_NCOUNT = 365, KVQ_READS_WORDS = 621 };
+enum { KVQ_DUP_LEVEL = 0, KVQ_DUP_SLOTS = 1, KVQ_DUP_KEYED = 2, KVQ_DUP_UNKEYED = 3, KVQ_DUP_TRACKED_RECORDS = 4, KVQ_DUP_TRACKED_KEYS = 5,
+       KVQ_DUP_DISTINCT = 8, KVQ_DUP_RECORDS = 24, KVQ_DUP_BINS = 16, KVQ_DUP_WORDS = 40 };
+#define KVQ_READ_STATS 1
+#define KVQ_READ_DUPLICATION 2
+#define KVQ_DUP_DEFAULT_SLOTS (1 << 24)
+#define KVQ_DUP_MIN_SLOTS 1024
+int64_t        kvq_reads_len(void);
+int64_t        kvq_dup_len(void);
+int32_t        kvq_scan_set_read_stats(kvq_scan *s, int32_t mode);
+const int64_t *kvq_scan_reads(const kvq_scan *s);
+const int64_t *kvq_scan_dup(const kvq_scan *s);
+/* host only, plain C++: the CPU twin of kvq_reads_records and the table over the same definition -- test infrastructure and
+ * the definition in running code, not a fallback.  Arguments as for kvq_profile_host; slots: C (<= 0: the default; otherwise
+ * clamped and rounded as KVQ_DUP_SLOTS is).  reads_out (or NULL): ADDS into [0, kvq_reads_len()).  dup_out (or NULL): WRITES
+ * [0, kvq_dup_len()) -- the level is found from the final key set, as it is defined.  kvq_dup_hash_host: the hash of the key of
+ * a bases line of L >= 1 bytes (kvq_dup_hash), for the tests. */
+int32_t        kvq_reads_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t slots,
+                              int64_t *reads_out, int64_t *dup_out);
+uint64_t       kvq_dup_hash_host(const uint8_t *line, int64_t L);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -280,6 +340,7 @@ double  kvq_scan_kernel_ms(const kvq_scan *s);
 double  kvq_scan_main_kernel_ms(const kvq_scan *s);
 double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_profile_records alone (0 when the profile is off) */
 double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_profile_cycles alone (0 when the cycles are off) */
+double  kvq_scan_reads_kernel_ms(const kvq_scan *s);     /* ... and for kvq_reads_records and the table's settle kernels (0 when both are off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 /* (measurement) how kvq_scan_finish put the hits of the finished scan in order:
@@ -425,6 +486,10 @@ kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
  * takes to the GPU (host reader, device inflate, BAM). */
 #define KVQ_FIND_LONG_READS 32u
 #define KVQ_FIND_LONG_READS_AUTO 64u
+/* KVQ_FIND_READ_STATS / KVQ_FIND_DUPLICATION: kvq_scan_set_read_stats bit 0 / bit 1 for the call (kvq_scan_reads / kvq_scan_dup
+ * after it); without KVQ_FIND_PROFILE they are KVQ_ERR_RUNTIME. */
+#define KVQ_FIND_READ_STATS 128u
+#define KVQ_FIND_DUPLICATION 256u
 typedef struct kvq_find_opts {
     uint32_t size, flags;
     int32_t  n_cutoffs;

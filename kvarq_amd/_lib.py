@@ -14,6 +14,8 @@ CELL_DENSE, CELL_DIAG, CELL_STAMPS = 0x1000, 0x2000, 0x4000      # kvq_scan_kern
 FIND_RECORDS = 4                                                 # kvq_findseqs_ex: keep the records of the hits
 FIND_PROFILE = 8                                                 # kvq_findseqs_opts: profile the input
 FIND_CYCLES = 16                                                 # ... and count its bytes per cycle (with FIND_PROFILE)
+FIND_READ_STATS, FIND_DUPLICATION = 128, 256                     # ... the per-read distributions, the duplication (with FIND_PROFILE)
+READ_STATS, READ_DUPLICATION = 1, 2                              # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
 PATH_READ_LIST = 0x80                                            # kvq_scan_path bit 7
@@ -117,6 +119,14 @@ PROTOTYPES = {
     'kvq_scan_set_cycles': (i32, [vp, i32]),
     'kvq_scan_cycles': (P(i64), [vp]),
     'kvq_cycles_host': (i32, [vp, i64, P(i64), i64, P(i64)]),
+    'kvq_reads_len': (i64, []),
+    'kvq_dup_len': (i64, []),
+    'kvq_scan_set_read_stats': (i32, [vp, i32]),
+    'kvq_scan_reads': (P(i64), [vp]),
+    'kvq_scan_dup': (P(i64), [vp]),
+    'kvq_reads_host': (i32, [vp, i64, P(i64), i64, i64, P(i64), P(i64)]),
+    'kvq_dup_hash_host': (u64, [vp, i64]),
+    'kvq_scan_reads_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

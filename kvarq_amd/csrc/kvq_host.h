@@ -189,8 +189,8 @@ struct kvq_scan {
     hipEvent_t ev_chain = nullptr;       // this scan's last seed-filter launch and its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles: what the next scan of the process waits for)
     int64_t parsed = 0, total = 0;
     // timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_prof, ev_cyc, ev_free;     // ev_prof: around kvq_profile_records; ev_cyc: around kvq_profile_cycles; ev_free: pairs of earlier scans, reused
-    double ms_all = 0, ms_main = 0, ms_prof = 0, ms_cyc = 0; int64_t main_launches = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_prof, ev_cyc, ev_reads, ev_free;     // ev_prof: around kvq_profile_records; ev_cyc: around kvq_profile_cycles; ev_reads: around kvq_reads_records and the table's settle; ev_free: pairs of earlier scans, reused
+    double ms_all = 0, ms_main = 0, ms_prof = 0, ms_cyc = 0, ms_reads = 0; int64_t main_launches = 0;
     // results: ordered and laid out on the device (kernels_results.hip), one copy into pinned host memory
     DevBuf d_sort_tmp, d_sorted, d_result, d_order, d_finish;   // d_order: bucket arrays of the ordering; d_finish: KvqFinishState
     uint32_t order_nb_max = 0;                    // the bucket arrays in d_order are laid out for this many buckets
@@ -226,6 +226,13 @@ struct kvq_scan {
     bool cycles_on = false;
     DevBuf d_cyc; int64_t *pin_cyc = nullptr; size_t pin_cyc_cap = 0;
     std::vector<int64_t> h_cyc;
+    // what the individual reads look like (kvq_scan_set_read_stats): bit 0 the per-read distributions (d_reads, its landing buffer,
+    // the finished scan's copy), bit 1 the duplication (d_dup: the state block, two tables of dup_slots slots, the result array
+    // kvq_dup_levels writes; KvqDupLayout).  There only while the bit is on
+    int32_t reads_mode = 0;
+    DevBuf d_reads, d_dup; int64_t *pin_reads = nullptr; size_t pin_reads_cap = 0;
+    uint64_t dup_slots = 0;
+    std::vector<int64_t> h_reads, h_dup;
 };
 
 // kernels_seeded.hip

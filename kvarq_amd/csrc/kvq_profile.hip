@@ -3,6 +3,7 @@
 // CPU twin of the kernel (the definition in plain C++: test infrastructure, never a fallback)
 #include "kvq_host.h"
 #include <string.h>
+#include <unordered_map>
 
 extern "C" int64_t kvq_profile_len(int32_t ncut)
 {
@@ -10,6 +11,7 @@ extern "C" int64_t kvq_profile_len(int32_t ncut)
 }
 
 static void cycles_off(kvq_scan *s);
+static void reads_off(kvq_scan *s);
 
 extern "C" int32_t kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int32_t ncut)
 {
@@ -18,7 +20,7 @@ extern "C" int32_t kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_profile: only before the first batch or after kvq_scan_reset");
         return KVQ_ERR_RUNTIME;
     }
-    if (ncut < 0) { s->profile_on = false; s->prof_ncut = 0; cycles_off(s); return KVQ_OK; }
+    if (ncut < 0) { s->profile_on = false; s->prof_ncut = 0; cycles_off(s); reads_off(s); return KVQ_OK; }
     if (ncut > KVQ_PROFILE_MAX_CUTOFFS || (ncut > 0 && !cutoffs)) {
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_profile: at most %d cutoffs", KVQ_PROFILE_MAX_CUTOFFS);
         return KVQ_ERR_RUNTIME;
@@ -170,7 +172,194 @@ static void cycles_landed(kvq_scan *s) { s->h_cyc.assign(s->pin_cyc, s->pin_cyc 
 
 extern "C" const int64_t *kvq_scan_cycles(const kvq_scan *s) { return s->cycles_on && s->finished && !s->h_cyc.empty() ? s->h_cyc.data() : nullptr; }
 
+// ---- per-read distributions and duplication (include/kvarq_hip.h): the same steps once more ----
+extern "C" int64_t kvq_reads_len(void) { return KVQ_READS_WORDS; }
+extern "C" int64_t kvq_dup_len(void) { return KVQ_DUP_WORDS; }
+
+// C from a wish: the default, or what the wish shrinks it to -- no less than KVQ_DUP_MIN_SLOTS, rounded down to a power of two
+static uint64_t dup_slots_from(long long wish)
+{
+    if (wish <= 0 || wish >= KVQ_DUP_DEFAULT_SLOTS) return KVQ_DUP_DEFAULT_SLOTS;
+    uint64_t c = KVQ_DUP_MIN_SLOTS;
+    while (2 * c <= (uint64_t)wish) c *= 2;
+    return c;
+}
+// where the pieces lie inside kvq_scan::d_dup: the state block, the result array of kvq_dup_levels, the two tables
+struct KvqDupLayout {
+    static constexpr size_t STATE = 0, RESULT = 1024, TABLES = 2048;
+    static_assert(KvqDupState::WORDS * 8 <= RESULT && RESULT + KVQ_DUP_WORDS * 8 <= TABLES, "the pieces of d_dup overlap");
+    static size_t bytes(uint64_t slots) { return TABLES + 2 * (size_t)slots * 16; }
+};
+static KvqDupTable dup_table(const kvq_scan *s)
+{
+    KvqDupTable T; T.state = nullptr; T.tab[0] = T.tab[1] = nullptr; T.lg = 0;
+    if (!(s->reads_mode & KVQ_READ_DUPLICATION)) return T;
+    char *p = (char *)s->d_dup.p;
+    T.state = (unsigned long long *)(p + KvqDupLayout::STATE);
+    T.tab[0] = (unsigned long long *)(p + KvqDupLayout::TABLES); T.tab[1] = T.tab[0] + 2 * s->dup_slots;
+    while ((1ull << T.lg) < s->dup_slots) T.lg++;
+    return T;
+}
+
+static void reads_off(kvq_scan *s)
+{
+    if (s->d_reads.p || s->d_dup.p) (void)hipStreamSynchronize(s->stream);       // (as cycles_off: a reset has enqueued their clearing)
+    if (s->pin_reads) pinned_give(s->pin_reads, s->pin_reads_cap);
+    s->pin_reads = nullptr; s->pin_reads_cap = 0;
+    s->d_reads.release(); s->d_dup.release();
+    s->h_reads.clear(); s->h_reads.shrink_to_fit(); s->h_dup.clear(); s->h_dup.shrink_to_fit();
+    s->reads_mode = 0; s->dup_slots = 0;
+}
+
+// the array AND the table back to zero: wherever the profile is cleared, so that a replay, a rescan round and a file read again
+// count every record once (a zero state block is level 0 with table 0 active)
+static int reads_clear(kvq_scan *s)
+{
+    if (s->reads_mode & KVQ_READ_STATS) KVQ_HIP(hipMemsetAsync(s->d_reads.p, 0, (size_t)KVQ_READS_WORDS * 8, s->stream));
+    if (s->reads_mode & KVQ_READ_DUPLICATION) KVQ_HIP(hipMemsetAsync(s->d_dup.p, 0, KvqDupLayout::bytes(s->dup_slots), s->stream));
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_scan_set_read_stats(kvq_scan *s, int32_t mode)
+{
+    kvq_clear_error();
+    if (!s->batches.empty() || s->copied_pending || s->host_pending >= 0) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_read_stats: only before the first batch or after kvq_scan_reset");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (!mode) { reads_off(s); return KVQ_OK; }
+    if (mode & ~(KVQ_READ_STATS | KVQ_READ_DUPLICATION)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_read_stats: mode is bit 0 (the distributions) and bit 1 (the duplication)");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (!s->profile_on) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_read_stats: the scan keeps no profile (the per-read statistics ride on its record set and index: kvq_scan_set_profile first)");
+        return KVQ_ERR_RUNTIME;
+    }
+    const char *e = getenv("KVQ_DUP_SLOTS");
+    const uint64_t slots = (mode & KVQ_READ_DUPLICATION) ? dup_slots_from(e ? atoll(e) : 0) : 0;
+    if (mode != s->reads_mode || slots != s->dup_slots) reads_off(s);        // (a kept scan object asked for the same again keeps its buffers)
+    int rc;
+    if ((mode & KVQ_READ_STATS) && (rc = s->d_reads.ensure((size_t)KVQ_READS_WORDS * 8))) return rc;
+    if ((mode & KVQ_READ_DUPLICATION) && (rc = s->d_dup.ensure(KvqDupLayout::bytes(slots)))) { reads_off(s); return rc; }
+    const size_t bytes = (size_t)(KVQ_READS_WORDS + KVQ_DUP_WORDS) * 8;
+    if (s->pin_reads_cap < bytes) {
+        if (s->pin_reads) pinned_give(s->pin_reads, s->pin_reads_cap);
+        s->pin_reads = (int64_t *)pinned_take(bytes, &s->pin_reads_cap);
+        if (!s->pin_reads) { s->pin_reads_cap = 0; reads_off(s); kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
+    }
+    s->reads_mode = mode; s->dup_slots = slots;
+    s->h_reads.clear(); s->h_dup.clear();
+    return reads_clear(s);
+}
+
+// the pass over the R records of a batch, behind its profile pass.  With the duplication the records go in slices of at most a
+// quarter of the table's slots, the settle behind every slice: with at most half the slots taken in front of a slice the table
+// is never more than three-quarters full, and no insert is ever refused
+static int reads_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    const bool dup = (s->reads_mode & KVQ_READ_DUPLICATION) != 0;
+    const KvqDupTable T = dup_table(s);
+    const uint64_t slice = dup ? s->dup_slots / 4 : R;
+    const uint32_t settle_grid = (uint32_t)std::min<uint64_t>(s->dup_slots / 256, KVQ_DUP_GRID_MAX);
+    for (uint64_t r0 = 0; r0 < R; r0 += slice) {
+        const uint64_t r1 = std::min(R, r0 + slice);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((r1 - r0 + 15) / 16, 2048);         // (the kernel strides over what there is)
+        hipLaunchKernelGGL(kvq_reads_records, dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)r0, (uint32_t)r1,
+                           (uint32_t)s->reads_mode, s->d_reads.as<unsigned long long>(), T);
+        if (dup) {
+            hipLaunchKernelGGL(kvq_dup_plan, dim3(settle_grid), dim3(256), 0, s->stream, T);
+            hipLaunchKernelGGL(kvq_dup_purge, dim3(settle_grid), dim3(256), 0, s->stream, T);
+        }
+    }
+    KVQ_HIP(hipGetLastError());
+    return KVQ_OK;
+}
+
+// the tail of a scan: the array, and what kvq_dup_levels makes of the active table, on their way to the host
+static int reads_tail(kvq_scan *s)
+{
+    if (s->reads_mode & KVQ_READ_STATS)
+        KVQ_HIP(hipMemcpyAsync(s->pin_reads, s->d_reads.p, (size_t)KVQ_READS_WORDS * 8, hipMemcpyDeviceToHost, s->stream));
+    if (s->reads_mode & KVQ_READ_DUPLICATION) {
+        unsigned long long *res = (unsigned long long *)((char *)s->d_dup.p + KvqDupLayout::RESULT);
+        KVQ_HIP(hipMemsetAsync(res, 0, (size_t)KVQ_DUP_WORDS * 8, s->stream));
+        hipLaunchKernelGGL(kvq_dup_levels, dim3((uint32_t)std::min<uint64_t>(s->dup_slots / 256, KVQ_DUP_GRID_MAX)), dim3(256), 0, s->stream, dup_table(s), res);
+        KVQ_HIP(hipGetLastError());
+        KVQ_HIP(hipMemcpyAsync(s->pin_reads + KVQ_READS_WORDS, res, (size_t)KVQ_DUP_WORDS * 8, hipMemcpyDeviceToHost, s->stream));
+    }
+    return KVQ_OK;
+}
+static void reads_landed(kvq_scan *s)
+{
+    if (s->reads_mode & KVQ_READ_STATS) s->h_reads.assign(s->pin_reads, s->pin_reads + KVQ_READS_WORDS);
+    if (s->reads_mode & KVQ_READ_DUPLICATION) s->h_dup.assign(s->pin_reads + KVQ_READS_WORDS, s->pin_reads + KVQ_READS_WORDS + KVQ_DUP_WORDS);
+}
+
+extern "C" const int64_t *kvq_scan_reads(const kvq_scan *s) { return (s->reads_mode & KVQ_READ_STATS) && s->finished && !s->h_reads.empty() ? s->h_reads.data() : nullptr; }
+extern "C" const int64_t *kvq_scan_dup(const kvq_scan *s) { return (s->reads_mode & KVQ_READ_DUPLICATION) && s->finished && !s->h_dup.empty() ? s->h_dup.data() : nullptr; }
+
 // ---- the twins ----
+extern "C" uint64_t kvq_dup_hash_host(const uint8_t *line, int64_t L) { return line && L > 0 ? kvq_dup_hash(line, (uint64_t)L) : 0; }
+
+extern "C" int32_t kvq_reads_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t slots,
+                                  int64_t *reads_out, int64_t *dup_out)
+{
+    kvq_clear_error();
+    bool ok = nbytes >= 0 && nchunks >= 0 && (nchunks == 0 || chunk_off);
+    for (int64_t c = 0; ok && c <= nchunks && nchunks > 0; c++) ok = chunk_off[c] >= 0 && chunk_off[c] <= nbytes && (!c || chunk_off[c] >= chunk_off[c - 1]);
+    if (!ok) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_reads_host: bad arguments"); return KVQ_ERR_RUNTIME; }
+    std::unordered_map<uint64_t, int64_t> keys;                                // every key of the input with its count
+    int64_t keyed = 0, unkeyed = 0;
+    for (int64_t c = 0; c < nchunks; c++) {
+        int64_t nl[4]; int have = 0;
+        for (int64_t i = chunk_off[c]; i < chunk_off[c + 1]; i++) {
+            if (text[i] != '\n') continue;
+            nl[have++] = i;
+            if (have < 4) continue;                                            // a complete record of the chunk
+            have = 0;
+            const uint8_t *bases = text + nl[0] + 1, *scores = text + nl[2] + 1;
+            int64_t L = nl[1] - nl[0] - 1, Q = nl[3] - nl[2] - 1;
+            if (L > 0 && bases[L - 1] == '\r') L--;                            // a trailing '\r' is not part of its line
+            if (Q > 0 && scores[Q - 1] == '\r') Q--;
+            if (reads_out) {
+                int64_t a = 0, g = 0, n = 0, S = 0;
+                for (int64_t j = 0; j < L; j++) {
+                    const uint8_t b = bases[j];
+                    a += b == 'A' || b == 'C' || b == 'G' || b == 'T'; g += b == 'G' || b == 'C'; n += b == 'N';
+                }
+                for (int64_t j = 0; j < Q; j++) S += scores[j];
+                reads_out[KVQ_READS_RECORDS]++;
+                if (a > 0) reads_out[KVQ_READS_GC + (200 * g + a) / (2 * a)]++; else reads_out[KVQ_READS_GC_NONE]++;
+                if (Q > 0) reads_out[KVQ_READS_MEANQ + (2 * S + Q) / (2 * Q)]++; else reads_out[KVQ_READS_MEANQ_NONE]++;
+                reads_out[KVQ_READS_NCOUNT + std::min<int64_t>(n, 255)]++;
+            }
+            if (dup_out) {
+                if (L == 0) unkeyed++;
+                else { keyed++; keys[kvq_dup_hash(bases, (uint64_t)L)]++; }
+            }
+        }
+    }
+    if (!dup_out) return KVQ_OK;
+    const uint64_t C = dup_slots_from(slots);
+    uint32_t level = 0;
+    for (;; level++) {                                                          // the smallest level with at most C / 2 distinct tracked keys
+        uint64_t tracked = 0;
+        for (const auto &k : keys) tracked += kvq_dup_tracked(k.first, level);
+        if (tracked <= C / 2) break;
+    }
+    memset(dup_out, 0, (size_t)KVQ_DUP_WORDS * 8);
+    dup_out[KVQ_DUP_LEVEL] = level; dup_out[KVQ_DUP_SLOTS] = (int64_t)C; dup_out[KVQ_DUP_KEYED] = keyed; dup_out[KVQ_DUP_UNKEYED] = unkeyed;
+    for (const auto &k : keys) {
+        if (!kvq_dup_tracked(k.first, level)) continue;
+        const uint32_t b = kvq_dup_bin((uint64_t)k.second);
+        dup_out[KVQ_DUP_DISTINCT + b]++; dup_out[KVQ_DUP_RECORDS + b] += k.second;
+        dup_out[KVQ_DUP_TRACKED_KEYS]++; dup_out[KVQ_DUP_TRACKED_RECORDS] += k.second;
+    }
+    return KVQ_OK;
+}
+
 extern "C" int32_t kvq_cycles_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t *out)
 {
     kvq_clear_error();

@@ -90,6 +90,7 @@ static int reset_device_state(kvq_scan *s)
     KVQ_HIP(hipGetLastError());
     if (s->profile_on) { const int rc = profile_clear(s); if (rc) return rc; }
     if (s->cycles_on) { const int rc = cycles_clear(s); if (rc) return rc; }
+    if (s->reads_mode) { const int rc = reads_clear(s); if (rc) return rc; }
     if (s->records_on) return records_prepare(s);
     return KVQ_OK;
 }
@@ -222,7 +223,7 @@ static void chain_forget(const kvq_scan *s)
 // timing events are kept for the next scan of the same handle (creating a pair costs several microseconds)
 static void drop_events(kvq_scan *s, bool destroy = false)
 {
-    for (auto *v : { &s->ev_all, &s->ev_main, &s->ev_prof, &s->ev_cyc }) { s->ev_free.insert(s->ev_free.end(), v->begin(), v->end()); v->clear(); }
+    for (auto *v : { &s->ev_all, &s->ev_main, &s->ev_prof, &s->ev_cyc, &s->ev_reads }) { s->ev_free.insert(s->ev_free.end(), v->begin(), v->end()); v->clear(); }
     if (destroy) {
         chain_forget(s);
         for (auto &e : s->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -246,7 +247,8 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
     if (s->pin_rec) pinned_give(s->pin_rec, s->pin_rec_cap);
     if (s->pin_prof) pinned_give(s->pin_prof, s->pin_prof_cap);
     if (s->pin_cyc) pinned_give(s->pin_cyc, s->pin_cyc_cap);
-    DevBuf *bufs[] = { &s->d_cyc, &s->d_prof, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
+    if (s->pin_reads) pinned_give(s->pin_reads, s->pin_reads_cap);
+    DevBuf *bufs[] = { &s->d_reads, &s->d_dup, &s->d_cyc, &s->d_prof, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
                        &s->d_rec_start, &s->d_read_off, &s->d_read_len, &s->d_arena, &s->d_blob, &s->d_small, &s->d_stage, &s->d_stage_b };
     for (DevBuf *b : bufs) b->release();
     s->pool.release();
@@ -292,7 +294,7 @@ extern "C" int32_t kvq_scan_reset(kvq_scan *s)
     drop_events(s);
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     s->batches.clear(); s->host_batches = false; s->host_pending = -1; s->copied_pending = false; s->parsed = 0; s->total = 0;
-    s->ms_all = s->ms_main = s->ms_prof = s->ms_cyc = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
+    s->ms_all = s->ms_main = s->ms_prof = s->ms_cyc = s->ms_reads = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
     s->tail_pending = false;
     s->pool.used = 0;
     const int rr = reset_device_state(s);
@@ -571,6 +573,12 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
                 KVQ_HIP(hipEventRecord(s->ev_cyc.back().first, s->stream));
                 if ((rc = cycles_enqueue(s, d_data, (uint64_t)B.nrec))) return rc;
                 KVQ_HIP(hipEventRecord(s->ev_cyc.back().second, s->stream));
+            }
+            if (s->reads_mode) {                          // ... and what the single reads look like, from the same index
+                if ((rc = new_event_pair(s, s->ev_reads))) return rc;
+                KVQ_HIP(hipEventRecord(s->ev_reads.back().first, s->stream));
+                if ((rc = reads_enqueue(s, d_data, (uint64_t)B.nrec))) return rc;
+                KVQ_HIP(hipEventRecord(s->ev_reads.back().second, s->stream));
             }
         }
     }

@@ -113,7 +113,7 @@ PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
 PATH_DEVICE_BAM = 0x40                             # kvq_scan_path bit 6
 
 
-def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, cycles=False, long_reads=False):
+def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
@@ -151,6 +151,11 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
     cycles=True: that profile also holds the per-cycle counts -- how often every byte stands at
     every position of the score and bases lines (``Profile.cycle_scores`` and what follows it;
     DESIGN section 14).  Without ``profile`` it means a profile with no cutoffs.
+
+    per_read=True / duplication=True: that profile also holds the per-read distributions (GC share,
+    mean quality, N count: ``Profile.gc_hist`` and what follows it) / how often the reads' first 64
+    bases repeat (``Profile.duplication``).  Without ``profile`` either means a
+    profile with no cutoffs.
 
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
@@ -199,13 +204,13 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
-    if cycles and profile is None:
+    if (cycles or per_read or duplication) and profile is None:
         profile = ()
     if profile is not None:
         from . import profile as profile_
         cuts = profile_.as_cutoffs(profile)
         opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | long_flag | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE |
-                             (_lib.FIND_CYCLES if cycles else 0),
+                             (_lib.FIND_CYCLES if cycles else 0) | (_lib.FIND_READ_STATS if per_read else 0) | (_lib.FIND_DUPLICATION if duplication else 0),
                              len(cuts), (C.c_uint8 * 8)(*cuts))
         h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opts))
     elif inflate == 'host' and not records and not long_flag:

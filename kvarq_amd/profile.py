@@ -12,6 +12,11 @@ take the profile along with a scan.  ``profile_host`` is the CPU twin of the ker
 and test infrastructure, not a fallback).  ``python -m kvarq_amd.profile FILE [-Q q ...]`` prints the summary,
 ``--cycles [--cycle-step N]`` a line per cycle (or per N cycles) behind it.
 
+With ``per_read=True`` the profile tells what the INDIVIDUAL READS look like: the histograms of the
+per-read GC share, mean quality and N count (``Profile.gc_hist`` and what follows it) -- a contaminant shows as a second
+GC peak that no sum over reads can show --, with ``duplication=True`` how often the reads' first 64 bases repeat
+(``Profile.duplication``, ``Profile.duplicate_share()``); ``--per-read`` and ``--duplication`` print them.
+
 Out of scope: profiles across ranks, and what ``Fastq`` guesses by default.
 """
 import ctypes as C
@@ -29,6 +34,13 @@ SCORE_BYTES, BASE_BYTES, RAW_LENGTHS, RAW_BINS, CUTOFFS, CUT_WORDS = 8, 264, 520
 
 CYCLES = 1024                                   # KVQ_CYCLES
 CYCLES_LEN = 2 * CYCLES * 256                   # kvq_cycles_len(): score[p][b] at p * 256 + b, base[p][b] behind them
+
+
+# the per-read distributions and the duplication (include/kvarq_hip.h: kvq_reads_len(), kvq_dup_len())
+READS_RECORDS, READS_GC_NONE, READS_MEANQ_NONE, READS_GC, READS_GC_BINS, READS_MEANQ, READS_NCOUNT, READS_LEN = 0, 1, 2, 8, 101, 109, 365, 621
+DUP_HEADER = ('level', 'slots', 'keyed', 'unkeyed', 'tracked_records', 'tracked_distinct')
+DUP_DISTINCT, DUP_RECORDS, DUP_BINS, DUP_LEN = 8, 24, 16, 40
+DUP_BOUNDS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)        # the lower bounds of the count bins
 
 
 def profile_len(ncut):
@@ -92,6 +104,16 @@ def _rows_quantile(rows, q, dQ):
     return np.where(total > 0, byte - 33.0 - dQ, np.nan)
 
 
+def _rows_quantile_raw(rows, q, dQ):
+    """``_rows_quantile`` over rows in which byte 13 is a value like the others (a mean, not a '\\r')"""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError('a quantile lies in 0 .. 1')
+    cum = np.cumsum(rows, axis=1)
+    total = cum[:, -1]
+    byte = (cum >= np.maximum(q * total, 1)[:, None]).argmax(axis=1)
+    return np.where(total > 0, byte - 33.0 - dQ, np.nan)
+
+
 def _rows_base_share(rows):
     acgtn = rows[:, [ord(c) for c in 'ACGTN']]
     total = rows.sum(axis=1)
@@ -102,10 +124,26 @@ class Profile(object):
     """a finished profile: ``records``, ``score_bytes`` / ``base_bytes`` (256 counts each), ``raw_lengths`` (1025 bins,
     the last one holding the lines of 1024 bytes and more), ``mismatched`` (records whose score and bases lines differ
     in length), ``longest`` (the longest bases line, -1: none), ``cutoffs`` (byte values), ``words`` (the flat array);
-    ``cycles``: the flat per-cycle array (kvq_cycles_len() words) when the scan took it, else None"""
+    ``cycles``: the flat per-cycle array (kvq_cycles_len() words) when the scan took it, else None;
+    ``reads``: the flat array of the per-read distributions (kvq_reads_len() words) when the scan took it, else None --
+    ``gc_hist`` (101 bins: the reads by their GC share in per cent), ``gc_none`` (reads without A C G T),
+    ``mean_quality_hist`` (256 bins: the reads by their mean score BYTE), ``n_hist`` (256 bins: the reads by their N
+    count, 255 and more in the last);
+    ``duplication``: a dict of the header words of kvq_scan_dup (``DUP_HEADER``) and its two rows of 16 bins,
+    'distinct' and 'records' (``DUP_BOUNDS``: their lower bounds), or None"""
 
-    def __init__(self, words, cutoffs, cycles=None):
+    def __init__(self, words, cutoffs, cycles=None, reads=None, dup=None):
         self.cutoffs = list(cutoffs)
+        self.reads = self.duplication = None
+        if reads is not None:
+            self.reads = np.array(reads, dtype=np.int64)
+            assert self.reads.shape == (READS_LEN,)
+        if dup is not None:
+            dup = np.array(dup, dtype=np.int64)
+            assert dup.shape == (DUP_LEN,)
+            self.duplication = dict(zip(DUP_HEADER, (int(v) for v in dup[:len(DUP_HEADER)])))
+            self.duplication['distinct'] = [int(v) for v in dup[DUP_DISTINCT:DUP_DISTINCT + DUP_BINS]]
+            self.duplication['records'] = [int(v) for v in dup[DUP_RECORDS:DUP_RECORDS + DUP_BINS]]
         self.cycles = None
         if cycles is not None:
             self.cycles = np.array(cycles, dtype=np.int64)
@@ -122,9 +160,12 @@ class Profile(object):
     def __eq__(self, other):
         if not (isinstance(other, Profile) and self.cutoffs == other.cutoffs and (self.words == other.words).all()):
             return False
-        if self.cycles is None or other.cycles is None:
-            return self.cycles is None and other.cycles is None
-        return bool((self.cycles == other.cycles).all())
+        if self.duplication != other.duplication:
+            return False
+        for a, b in ((self.reads, other.reads), (self.cycles, other.cycles)):
+            if (a is None) != (b is None) or (a is not None and not (a == b).all()):
+                return False
+        return True
 
     def __ne__(self, other):
         return not self == other
@@ -254,6 +295,86 @@ class Profile(object):
                                               ' '.join('%.3f' % v for v in share[i, :5])))
         return lines
 
+    # -- per read ----------------------------------------------------------------
+
+    def _reads(self):
+        if self.reads is None:
+            raise ValueError('this profile was taken without per_read=True')
+        return self.reads
+
+    @property
+    def gc_hist(self):
+        """(101,): the reads by their GC share in per cent (G + C among A C G T, round half up)"""
+        return self._reads()[READS_GC:READS_GC + READS_GC_BINS]
+
+    @property
+    def gc_none(self):
+        """the reads whose bases line holds no A C G T"""
+        return int(self._reads()[READS_GC_NONE])
+
+    @property
+    def mean_quality_hist(self):
+        """(256,): the reads by the mean byte of their score line (round half up); ``mean_quality_per_read`` in PHRED"""
+        return self._reads()[READS_MEANQ:READS_MEANQ + 256]
+
+    @property
+    def n_hist(self):
+        """(256,): the reads by the number of N on their bases line, 255 and more in the last bin"""
+        return self._reads()[READS_NCOUNT:READS_NCOUNT + 256]
+
+    def gc_mean(self):
+        """the mean of the reads' GC shares in per cent (of the bins); nan when no read has A C G T"""
+        n = int(self.gc_hist.sum())
+        return float((self.gc_hist * np.arange(READS_GC_BINS)).sum()) / n if n else float('nan')
+
+    def mean_quality_per_read(self, dQ=None):
+        """{PHRED value: reads whose mean score rounds to it} over the bins that are not empty; ``dQ`` None: :meth:`dQ`"""
+        dQ = self.dQ() if dQ is None else dQ
+        return {int(b) - 33 - dQ: int(self.mean_quality_hist[b]) for b in np.nonzero(self.mean_quality_hist)[0]}
+
+    def mean_quality_quantile(self, q, dQ=None):
+        """the lowest PHRED value whose cumulative count reaches ``q`` (0 .. 1) of the reads' mean scores; nan: no read has scores"""
+        return float(_rows_quantile_raw(self.mean_quality_hist[None, :], q, self.dQ() if dQ is None else dQ)[0])
+
+    def duplicate_share(self):
+        """1 - tracked distinct keys / tracked records: the share of the (sampled) reads that repeat an earlier one;
+        nan when no read has a key"""
+        d = self.duplication
+        if d is None:
+            raise ValueError('this profile was taken without duplication=True')
+        return 1.0 - d['tracked_distinct'] / float(d['tracked_records']) if d['tracked_records'] else float('nan')
+
+    def per_read_lines(self, dQ=None):
+        """the per-read part of the command line: the GC histogram in 5 % steps with its mean, the quantiles of the reads'
+        mean quality, the share of reads with any N"""
+        if dQ is None:
+            try:
+                dQ = self.dQ()
+            except FastqFileFormatException:
+                dQ = 0
+        gc, n = self.gc_hist, int(self.gc_hist.sum())
+        lines = ['per-read GC: mean=%.1f%% reads=%d none=%d' % (self.gc_mean(), n, self.gc_none)]
+        for a in range(0, READS_GC_BINS, 5):
+            part = int(gc[a:a + 5].sum())
+            lines.append('GC %3d-%3d%% %d %.4f' % (a, min(a + 4, 100), part, part / float(n) if n else 0.0))
+        lines.append('per-read mean quality (dQ=%d): %s' % (dQ, ' '.join('Q%d=%g' % (int(q * 100), self.mean_quality_quantile(q, dQ)) for q in (0.1, 0.25, 0.5, 0.75, 0.9))))
+        total = int(self.n_hist.sum())
+        lines.append('reads with any N: %d of %d (%.4f)' % (total - int(self.n_hist[0]), total, (total - int(self.n_hist[0])) / float(total) if total else 0.0))
+        return lines
+
+    def duplication_lines(self):
+        """the duplication part of the command line: level and sample size, then a line per count bin"""
+        d = self.duplication
+        if d is None:
+            raise ValueError('this profile was taken without duplication=True')
+        lines = ['duplication: level=%d (1 of %d distinct sequences) slots=%d keyed=%d unkeyed=%d tracked: %d reads, %d distinct, duplicate share %.4f'
+                 % (d['level'], 1 << d['level'], d['slots'], d['keyed'], d['unkeyed'], d['tracked_records'], d['tracked_distinct'], self.duplicate_share())]
+        for i, lo_ in enumerate(DUP_BOUNDS):
+            hi = '%d' % (DUP_BOUNDS[i + 1] - 1) if i + 1 < len(DUP_BOUNDS) else ''
+            span = '%d' % lo_ if hi == '%d' % lo_ else '%d+' % lo_ if not hi else '%d-%s' % (lo_, hi)
+            lines.append('copies %s: distinct=%d reads=%d' % (span, d['distinct'][i], d['records'][i]))
+        return lines
+
     def summary(self):
         lines = ['records=%d mismatched=%d longest=%d' % (self.records, self.mismatched, self.longest)]
         lo_, hi = self.score_range()
@@ -280,6 +401,13 @@ class Profile(object):
             def sparse(rows):
                 return [{int(b): int(row[b]) for b in np.nonzero(row)[0]} for row in rows[:self.last_cycle + 1]]
             d['cycles'] = {'score': sparse(self.cycle_scores), 'base': sparse(self.cycle_bases)}
+        if self.reads is not None:
+            def bins(h):
+                return {int(b): int(h[b]) for b in np.nonzero(h)[0]}
+            d['per_read'] = {'records': int(self.reads[READS_RECORDS]), 'gc_none': self.gc_none, 'meanq_none': int(self.reads[READS_MEANQ_NONE]),
+                             'gc': bins(self.gc_hist), 'mean_quality_byte': bins(self.mean_quality_hist), 'n': bins(self.n_hist)}
+        if self.duplication is not None:
+            d['duplication'] = dict(self.duplication, bounds=list(DUP_BOUNDS))
         return d
 
 
@@ -290,14 +418,16 @@ def from_scan(L, h):
     ptr = L.kvq_scan_profile(h)
     if n < 0 or not ptr:
         return None
-    cyc = L.kvq_scan_cycles(h)
+    cyc, reads, dup = L.kvq_scan_cycles(h), L.kvq_scan_reads(h), L.kvq_scan_dup(h)
     return Profile(np.ctypeslib.as_array(ptr, shape=(profile_len(n),)).copy(), list(cuts)[:n],
-                   np.ctypeslib.as_array(cyc, shape=(CYCLES_LEN,)).copy() if cyc else None)
+                   np.ctypeslib.as_array(cyc, shape=(CYCLES_LEN,)).copy() if cyc else None,
+                   np.ctypeslib.as_array(reads, shape=(READS_LEN,)).copy() if reads else None,
+                   np.ctypeslib.as_array(dup, shape=(DUP_LEN,)).copy() if dup else None)
 
 
-def profile_host(text, cutoffs=(), chunk_off=None, cycles=False):
-    """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host) over a text in host memory; chunk_off None: the
-    reader's chunk cuts"""
+def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False, duplication=False, slots=0):
+    """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host; per_read / duplication: and kvq_reads_host, with a
+    table of ``slots`` slots, 0: the default) over a text in host memory; chunk_off None: the reader's chunk cuts"""
     from . import scan
     cuts = as_cutoffs(cutoffs)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
@@ -313,14 +443,22 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False):
         if _lib.lib().kvq_cycles_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)),
                                       len(co) - 1, cyc.ctypes.data_as(C.POINTER(C.c_int64))):
             raise RuntimeError(_lib.last_error()[1])
-    return Profile(out, cuts, cyc)
+    reads = np.zeros(READS_LEN, dtype=np.int64) if per_read else None
+    dup = np.zeros(DUP_LEN, dtype=np.int64) if duplication else None
+    if per_read or duplication:
+        if _lib.lib().kvq_reads_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1, int(slots),
+                                     reads.ctypes.data_as(C.POINTER(C.c_int64)) if per_read else None,
+                                     dup.ctypes.data_as(C.POINTER(C.c_int64)) if duplication else None):
+            raise RuntimeError(_lib.last_error()[1])
+    return Profile(out, cuts, cyc, reads, dup)
 
 
-def profile(fnames, cutoffs=True, inflate='host', cycles=False, long_reads=False):
+def profile(fnames, cutoffs=True, inflate='host', cycles=False, long_reads=False, per_read=False, duplication=False):
     """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
-    per-cycle counts"""
+    per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication"""
     from . import engine
-    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, cycles=cycles, long_reads=long_reads)['profile']
+    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, cycles=cycles, long_reads=long_reads,
+                           per_read=per_read, duplication=duplication)['profile']
 
 
 def main(argv=None):
@@ -332,14 +470,21 @@ def main(argv=None):
     ap.add_argument('--inflate', default='host', choices=sorted(engine.INFLATE_FLAGS))
     ap.add_argument('--cycles', action='store_true', help='a line per cycle: reads reaching it, mean Q, 10/50/90 %% quantiles, shares of A C G T N')
     ap.add_argument('--cycle-step', type=int, default=1, metavar='N', help='a line per N cycles')
+    ap.add_argument('--per-read', action='store_true', help='the per-read GC histogram in 5 %% steps with its mean, the quantiles of the per-read mean quality, the share of reads with any N')
+    ap.add_argument('--duplication', action='store_true', help='how often the first 64 bases of the reads repeat: level, sample size and a line per count bin')
     a = ap.parse_args(argv)
-    p = profile(a.files, cutoffs=True, inflate=a.inflate, cycles=a.cycles and not a.quality)
+    more = dict(per_read=a.per_read, duplication=a.duplication)
+    p = profile(a.files, cutoffs=True, inflate=a.inflate, cycles=a.cycles and not a.quality, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
-        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate, cycles=a.cycles)
+        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate, cycles=a.cycles, **more)
     print(p.summary())
     if a.cycles:
         print('\n'.join(p.cycle_lines(a.cycle_step)))
+    if a.per_read:
+        print('\n'.join(p.per_read_lines()))
+    if a.duplication:
+        print('\n'.join(p.duplication_lines()))
 
 
 if __name__ == '__main__':

@@ -96,7 +96,7 @@ class Scanner(object):
     ``finish`` raises ``RescanRequired`` and the caller, who has the data, resets and feeds again; a caller with
     a re-readable source passes ``replay=callable`` (called with the scanner after ``reset()``) instead."""
 
-    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None, cycles=False, long_reads=False):
+    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False):
         self.table = table
         long_mode = _lib.long_reads_mode(long_reads)
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
@@ -107,8 +107,10 @@ class Scanner(object):
             _check(_lib.lib().kvq_scan_set_records(self.h, 1))
         # profile the input at these cutoffs (kvarq_amd.profile.as_cutoffs; True: the table's Amin); kept across reset
         # cycles: the per-cycle counts beside the profile (kvq_scan_set_cycles); without ``profile``: a profile with no cutoffs
+        # per_read / duplication: the per-read distributions / the duplication beside it (kvq_scan_set_read_stats), in the same way
         self.profile, self.cycles = None, bool(cycles)
-        if self.cycles and profile is None:
+        self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
+        if (self.cycles or self.read_stats) and profile is None:
             profile = ()
         if profile is not None:
             from . import profile as profile_
@@ -116,6 +118,8 @@ class Scanner(object):
             _check(_lib.lib().kvq_scan_set_profile(self.h, (C.c_uint8 * 8)(*self.profile), len(self.profile)))
             if self.cycles:
                 _check(_lib.lib().kvq_scan_set_cycles(self.h, 1))
+            if self.read_stats:
+                _check(_lib.lib().kvq_scan_set_read_stats(self.h, self.read_stats))
         # the read-list route for reads of thousands of bases (kvq_scan_set_long_reads; True, or 'auto': by each batch's head); kept across reset
         self.long_reads = long_reads
         if long_mode:
@@ -210,6 +214,8 @@ class Scanner(object):
             out['profile_kernel_ms'] = L.kvq_scan_profile_kernel_ms(self.h)
             if self.cycles:
                 out['cycles_kernel_ms'] = L.kvq_scan_cycles_kernel_ms(self.h)
+            if self.read_stats:
+                out['reads_kernel_ms'] = L.kvq_scan_reads_kernel_ms(self.h)
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
