@@ -335,6 +335,12 @@ KVQ_HD int kvq_dyn_header(const G &g, KvqBits &br, uint8_t *lens, int *pnlen, in
     uint8_t cnt[8], sym[19], offs[8];
     for (int l = 0; l < 8; l++) cnt[l] = 0;
     for (int s = 0; s < 19; s++) cnt[cl[s]]++;
+    if (cnt[0] == 19) {
+        // zlib takes a code-length code without codes, reads every length as one bit and then misses the end-of-block code:
+        // a file cut short within those bits ends its text there
+        for (int i = 0; i < nlen + ndist; i += 32) (void)br.get(nlen + ndist - i < 32 ? nlen + ndist - i : 32);
+        return br.over() ? KVQ_INF_BUF_ERROR : KVQ_INF_DATA_ERROR;
+    }
     {
         uint8_t c16[16];
         for (int l = 0; l < 16; l++) c16[l] = l < 8 ? cnt[l] : 0;

@@ -21,7 +21,8 @@ limit, so invalid streams are made by overriding one field of a valid block.  A 
 
 A symbol without a code is written as nothing.  build(blocks) -> (payload, text): text is what the
 tokens mean (a copy reaching before the start reads zeros), the bytes a decoder must produce when
-the stream is valid.
+the stream is valid.  build(blocks, starts=[]) also reports where each block starts, in bits of the
+payload and in bytes of the text.
 
 inflate(payload, isize) is a slow puff.c-style inflater under zlib's rules (its one exception for an
 incomplete code: a single code of one bit in a literal/length or distance code) and the host reader's
@@ -186,12 +187,15 @@ def dynamic_header(b):
     return lit_lens, dist_lens, hlit, hdist, all_lens, rle, cl_lens, hclen
 
 
-def build(blocks):
-    """-> (payload, text)"""
+def build(blocks, starts=None):
+    """-> (payload, text).  starts (a list, filled in): per block the (bit offset in the payload, offset in the text) at
+    which it starts, and one more pair for the end of the last block"""
     bw, text = BitWriter(), bytearray()
     for bi, b in enumerate(blocks):
         final = b.get('final', bi == len(blocks) - 1)
         kind = b['kind']
+        if starts is not None:
+            starts.append((8 * len(bw.out) + bw.n, len(text)))
         bw.put(1 if final else 0, 1)
         if kind == 'stored':
             data = b.get('data', b'')
@@ -242,6 +246,8 @@ def build(blocks):
         if b.get('eob', True):
             bw.code(lit, 256)
         _expand(tokens, text)
+    if starts is not None:
+        starts.append((8 * len(bw.out) + bw.n, len(text)))
     return bw.bytes(), bytes(text)
 
 

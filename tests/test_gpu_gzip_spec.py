@@ -46,8 +46,9 @@ def _device(data, chunk_bytes, cap=None):
         d_out.free()
 
 
-def _same_as_host(data, chunk_bytes):
-    """the device run equals the host run, every chunk slot of both between canaries"""
+def _same_as_host(data, chunk_bytes, seen=None):
+    """the device run equals the host run, every chunk slot of both between canaries.  seen(chunks): a check of the caller's on
+    the device run's last_chunks(), made in front of the comparison"""
     G.slot_canaries(256)
     try:
         h_text, h_rep = G.inflate_host(data, chunk_bytes)
@@ -55,6 +56,8 @@ def _same_as_host(data, chunk_bytes):
         d_text, d_rep, d_chunks = _device(data, chunk_bytes, cap=len(h_text) + 4096)
     finally:
         assert G.slot_canaries(0) == 0, 'a decode wrote outside its slot'
+    if seen:
+        seen(d_chunks)
 
     assert d_text == h_text == host_reader(data)
     counts = lambda r: {k: v for k, v in r.items() if not k.startswith("ms_")}
