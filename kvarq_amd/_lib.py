@@ -4,6 +4,8 @@ every compute entry point reports KVQ_ERR_DEVICE."""
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 PATH = os.path.join(HERE, 'libkvarq_hip.so')
 
@@ -18,7 +20,10 @@ FIND_READ_STATS, FIND_DUPLICATION = 128, 256                     # ... the per-r
 READ_STATS, READ_DUPLICATION = 1, 2                              # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
-PATH_READ_LIST = 0x80                                            # kvq_scan_path bit 7
+# kvq_scan_path: a batch took the seed-filter kernel / the exhaustive kernels; a whole batch / the records of skipped tiles were redone;
+# the text was inflated on the device (bit 4; bit 5: a file by speculative gzip decoding; bit 6: BAM records); a batch took the read-list route
+PATH_SEEDED, PATH_EXHAUSTIVE, PATH_RESCANNED, PATH_TILES_RESCANNED = 1, 2, 4, 8
+PATH_DEVICE_INFLATE, PATH_DEVICE_GZIP, PATH_DEVICE_BAM, PATH_READ_LIST = 0x10, 0x20, 0x40, 0x80
 
 
 def long_reads_mode(long_reads):
@@ -213,6 +218,14 @@ def lib():
             f.restype, f.argtypes = res, args
         _lib = L
     return _lib
+
+
+def view(ptr, n, ctype, dtype):
+    """numpy view of a C array the library owns (np.ctypeslib.as_array costs ~60 us per call)"""
+    addr = C.cast(ptr, C.c_void_p).value
+    if not addr or n <= 0:
+        return np.zeros(0, dtype=dtype)
+    return np.frombuffer((ctype * n).from_address(addr), dtype=dtype)
 
 
 def kernel_cell(cell):

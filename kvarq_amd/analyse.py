@@ -64,14 +64,15 @@ class Analyser(object):
 
     # -- scanning ------------------------------------------------------------------
 
-    def scan(self, fastq, templates, do_reverse=True, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False):
+    def scan(self, fastq, templates, do_reverse=True, **options):
         """``fastq``: a :class:`kvarq_amd.fastq.Fastq`; ``templates``: ordered mapping name -> plus-strand
         template (``Sequence``, text, or ``(text, left, right)``).  May raise ``FastqFileFormatException``.
         ``records=True`` keeps the FastQ record of every hit, gathered on the GPU during the scan, for
         :meth:`extract_hits`.  ``profile=<cutoffs>`` keeps the ``kvarq_amd.profile.Profile`` of the input in
         ``self.profile`` (``encode`` then adds ``info['profile']``); ``cycles=True`` takes the per-cycle counts into it
         (``info['profile']['cycles']``), ``per_read=True`` / ``duplication=True`` the per-read distributions / the
-        duplication (``info['profile']['per_read']`` / ``['duplication']``)."""
+        duplication (``info['profile']['per_read']`` / ``['duplication']``); ``long_reads``: as for ``engine.findseqs``,
+        which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
         self.fastq_sizes = fastq.filesizes()
@@ -83,8 +84,7 @@ class Analyser(object):
         if do_reverse:
             seqs += [c.minus_seq.bases for c in self.coverages.values()]
         t0 = time.time()
-        ret = engine.findseqs(self.fastq_filenames, seqs, records=records, profile=profile, cycles=cycles, long_reads=long_reads,
-                              per_read=per_read, duplication=duplication)
+        ret = engine.findseqs(self.fastq_filenames, seqs, **options)
         lo.debug('found %d hits' % len(ret['hits']))
         self.stats, self.hits, self.hitseqs = ret['stats'], ret['hits'], ret['hitseqs']
         self.records = ret.get('records')

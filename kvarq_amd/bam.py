@@ -198,11 +198,12 @@ class Bam(object):
     def Q2A(self, Q):
         return ASCII[Q + self.dQ]
 
-    def profile(self, cutoffs=None, cycles=False, long_reads=False, per_read=False, duplication=False):
+    def profile(self, cutoffs=None, **options):
         """a ``kvarq_amd.profile.Profile`` of the file's virtual FastQ text, taken on the GPU; cutoffs None: the
-        configured Amin; ``cycles``: with the per-cycle counts; ``long_reads``: as for ``engine.findseqs``"""
+        configured Amin; ``cycles``: with the per-cycle counts; ``long_reads``: as for ``engine.findseqs``
+        (``options``: as for ``kvarq_amd.profile.profile``)"""
         from . import profile as profile_
-        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs, cycles=cycles, long_reads=long_reads, per_read=per_read, duplication=duplication)
+        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs, **options)
 
     def readrecordat(self, hit):
         raise IOError('the records of a BAM file are kept by the scan only: use Analyser.scan(..., records=True) '

@@ -238,7 +238,7 @@ extern "C" int32_t kvq_scan_set_comm(kvq_scan *s, kvq_comm *c)
         kvq_set_error(KVQ_ERR_RUNTIME, "records are not gathered across ranks: a scan that keeps records cannot take a communicator");
         return KVQ_ERR_RUNTIME;
     }
-    if (c && s->profile_on) {
+    if (c && s->passes[KVQ_PASS_PROFILE].on) {
         kvq_set_error(KVQ_ERR_RUNTIME, "the profile is not reduced across ranks: a scan that keeps one cannot take a communicator");
         return KVQ_ERR_RUNTIME;
     }

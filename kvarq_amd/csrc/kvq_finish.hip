@@ -147,9 +147,7 @@ static int enqueue_tail(kvq_scan *s)
     if (!s->tail_mergesort &&
         (rc = kvq_order_by_buckets(s->stream, s->d_arena.as<KvqHit>(), s->d_blob.as<uint8_t>(), s->blob_cap, d_st, W, s->d_result.as<uint8_t>()))) return rc;
     if (s->records_on && (rc = records_tail(s, d_st))) return rc;
-    if (s->profile_on && (rc = profile_tail(s))) return rc;
-    if (s->cycles_on && (rc = cycles_tail(s))) return rc;
-    if (s->reads_mode && (rc = reads_tail(s))) return rc;
+    if ((rc = passes_tail(s))) return rc;
     hipLaunchKernelGGL(kvq_publish_small, dim3(1), dim3(256), 0, s->stream, (const unsigned int *)s->d_small.p,
                        (const unsigned int *)s->d_fail, (unsigned int)nb0, (const unsigned int *)d_st, (unsigned int)(sizeof(KvqFinishState) / 4),
                        H.small, H.fail, H.state);
@@ -228,12 +226,13 @@ static int grow_landing(kvq_scan *s, size_t need, size_t ctr_b)
 
 static void sum_timing(kvq_scan *s)
 {
-    s->ms_all = s->ms_main = s->ms_prof = s->ms_cyc = s->ms_reads = 0;
-    for (auto &e : s->ev_all) { float ms = 0; if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) s->ms_all += ms; }
-    for (auto &e : s->ev_main) { float ms = 0; if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) s->ms_main += ms; }
-    for (auto &e : s->ev_prof) { float ms = 0; if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) s->ms_prof += ms; }
-    for (auto &e : s->ev_cyc) { float ms = 0; if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) s->ms_cyc += ms; }
-    for (auto &e : s->ev_reads) { float ms = 0; if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) s->ms_reads += ms; }
+    auto sum = [](const std::vector<KvqEventPair> &v) {
+        double total = 0;
+        for (auto &e : v) { float ms = 0; if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) total += ms; }
+        return total;
+    };
+    s->ms_all = sum(s->ev_all); s->ms_main = sum(s->ev_main);
+    for (KvqPass &p : s->passes) p.ms = sum(p.ev);
     (void)hipGetLastError();                 // (a pair that was never recorded is not an error of the scan)
 }
 
@@ -286,9 +285,7 @@ static int finish_once(kvq_scan *s)
         }
         if (s->records_on && (rc = records_fetch(s, n_hits, rec_used))) return rc;
         memcpy(s->h_ctr.data(), s->pin, (size_t)t->ctr_len * 8);
-        if (s->profile_on) profile_landed(s);
-        if (s->cycles_on) cycles_landed(s);
-        if (s->reads_mode) reads_landed(s);
+        passes_landed(s);
         s->pin_res = s->pin + ctr_b;
         if (!n_hits) memset(s->pin_res + L.hitseq_off, 0, 8);
         s->res = L; s->n_hits = n_hits;
@@ -404,9 +401,9 @@ extern "C" int64_t kvq_scan_parsed(const kvq_scan *s) { return s->parsed; }
 extern "C" int64_t kvq_scan_total(const kvq_scan *s) { return s->total; }
 extern "C" double kvq_scan_kernel_ms(const kvq_scan *s) { return s->ms_all; }
 extern "C" double kvq_scan_main_kernel_ms(const kvq_scan *s) { return s->ms_main; }
-extern "C" double kvq_scan_profile_kernel_ms(const kvq_scan *s) { return s->ms_prof; }
-extern "C" double kvq_scan_cycles_kernel_ms(const kvq_scan *s) { return s->ms_cyc; }
-extern "C" double kvq_scan_reads_kernel_ms(const kvq_scan *s) { return s->ms_reads; }
+extern "C" double kvq_scan_profile_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_PROFILE].ms; }
+extern "C" double kvq_scan_cycles_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_CYCLES].ms; }
+extern "C" double kvq_scan_reads_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_READS].ms; }
 // (measurement) ms from the end of a's last main kernel to the start of b's first one (both finished, neither reset since); < 0: unknown
 extern "C" double kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b)
 {

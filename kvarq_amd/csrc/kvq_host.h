@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string>
 #include <unistd.h>
+#include <utility>
 #include <vector>
 
 #include "../../include/kvarq_hip.h"
@@ -139,6 +140,19 @@ uint32_t kvq_device_cu_count();       // compute units of the current device
 int kvq_comm_reduce_counters(kvq_comm *c, const unsigned long long *d_in, unsigned long long *d_out, int64_t ctr_len, unsigned long long *d_scratch, hipStream_t stream);
 int kvq_comm_max_status(kvq_comm *c, unsigned long long mine, unsigned long long *d_scratch, hipStream_t stream, unsigned long long *out);
 
+// An input pass: a kernel that every batch runs once over its exact record index and that adds to one device array, which the
+// tail of the scan brings to the host.  The cycles' array has the kernel's own scratch word behind the words that land.
+enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASSES };
+typedef std::pair<hipEvent_t, hipEvent_t> KvqEventPair;
+struct KvqPass {
+    bool on = false;
+    DevBuf d; size_t d_bytes = 0;                       // the device array, and what of it is cleared
+    int64_t *pin = nullptr; size_t pin_cap = 0;         // its pinned landing buffer
+    size_t words = 0;                                   // the words of d that land
+    std::vector<int64_t> h;                             // the finished scan's copy
+    std::vector<KvqEventPair> ev; double ms = 0;        // around the pass's kernels of every batch; their sum
+};
+
 struct kvq_scan {
     const kvq_table *t = nullptr;
     kvq_comm *comm = nullptr;            // several GPUs: `finish` sums the counters of all ranks over it (kvq_dist.hip)
@@ -189,8 +203,8 @@ struct kvq_scan {
     hipEvent_t ev_chain = nullptr;       // this scan's last seed-filter launch and its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles: what the next scan of the process waits for)
     int64_t parsed = 0, total = 0;
     // timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_all, ev_main, ev_prof, ev_cyc, ev_reads, ev_free;     // ev_prof: around kvq_profile_records; ev_cyc: around kvq_profile_cycles; ev_reads: around kvq_reads_records and the table's settle; ev_free: pairs of earlier scans, reused
-    double ms_all = 0, ms_main = 0, ms_prof = 0, ms_cyc = 0, ms_reads = 0; int64_t main_launches = 0;
+    std::vector<KvqEventPair> ev_all, ev_main, ev_free;     // ev_free: pairs of earlier scans, reused (the passes below have their own)
+    double ms_all = 0, ms_main = 0; int64_t main_launches = 0;
     // results: ordered and laid out on the device (kernels_results.hip), one copy into pinned host memory
     DevBuf d_sort_tmp, d_sorted, d_result, d_order, d_finish;   // d_order: bucket arrays of the ordering; d_finish: KvqFinishState
     uint32_t order_nb_max = 0;                    // the bucket arrays in d_order are laid out for this many buckets
@@ -216,24 +230,20 @@ struct kvq_scan {
     uint64_t rec_tail_n = 0, rec_tail_b = 0;      // what the tail fetched ahead of time (offsets / lengths of that many hits, that many store bytes)
     uint64_t rec_spec_n = 4096, rec_spec_b = 1u << 20;   // ... guessed from the last scan of this handle
     int64_t rec_store_bytes = 0;                  // store bytes of the finished scan
-    // the profile of the input (kvq_scan_set_profile, kvq_profile.hip): the device array every batch's kvq_profile_records adds to,
-    // its pinned landing buffer, the finished scan's copy
-    bool profile_on = false; int32_t prof_ncut = 0; uint8_t prof_cuts[KVQ_PROFILE_MAX_CUTOFFS] = { 0 };
-    DevBuf d_prof; int64_t *pin_prof = nullptr; size_t pin_prof_cap = 0;
-    std::vector<int64_t> h_prof;
-    // the per-cycle counts beside it (kvq_scan_set_cycles): the same three, there only while the option is on; the device array
-    // has the kernel's own scratch word behind its kvq_cycles_len() words
-    bool cycles_on = false;
-    DevBuf d_cyc; int64_t *pin_cyc = nullptr; size_t pin_cyc_cap = 0;
-    std::vector<int64_t> h_cyc;
-    // what the individual reads look like (kvq_scan_set_read_stats): bit 0 the per-read distributions (d_reads, its landing buffer,
-    // the finished scan's copy), bit 1 the duplication (d_dup: the state block, two tables of dup_slots slots, the result array
-    // kvq_dup_levels writes; KvqDupLayout).  There only while the bit is on
+    // the passes over a batch's exact record index (kvq_profile.hip; DESIGN section 13, "the lifecycle of an input pass"), in the
+    // order they run: the profile of the input (kvq_scan_set_profile), the per-cycle counts beside it (kvq_scan_set_cycles) and what
+    // the individual reads look like (kvq_scan_set_read_stats).  The last two keep their buffers only while they are on
+    KvqPass passes[KVQ_PASSES];
+    int32_t prof_ncut = 0; uint8_t prof_cuts[KVQ_PROFILE_MAX_CUTOFFS] = { 0 };      // the profile's cutoffs
+    // the reads pass: bit 0 of its mode the per-read distributions (the pass's array), bit 1 the duplication (d_dup: the state block,
+    // two tables of dup_slots slots, the result array kvq_dup_levels writes; KvqDupLayout), which lands behind the distributions
     int32_t reads_mode = 0;
-    DevBuf d_reads, d_dup; int64_t *pin_reads = nullptr; size_t pin_reads_cap = 0;
-    uint64_t dup_slots = 0;
-    std::vector<int64_t> h_reads, h_dup;
+    DevBuf d_dup; uint64_t dup_slots = 0;
+    std::vector<int64_t> h_dup;
 };
+
+// kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal
+int scan_idle(const kvq_scan *s, const char *who);
 
 // kernels_seeded.hip
 struct SeedIndex;

@@ -88,9 +88,7 @@ static int reset_device_state(kvq_scan *s)
     hipLaunchKernelGGL(kvq_reset_state, dim3(256), dim3(256), 0, s->stream, (unsigned long long *)s->d_small.p, KvqSmall::BYTES / 8,
                        s->d_ctr, (size_t)s->t->ctr_len, s->d_covdiff.as<unsigned long long>(), (size_t)s->t->bases + (size_t)s->t->nseq + 1);
     KVQ_HIP(hipGetLastError());
-    if (s->profile_on) { const int rc = profile_clear(s); if (rc) return rc; }
-    if (s->cycles_on) { const int rc = cycles_clear(s); if (rc) return rc; }
-    if (s->reads_mode) { const int rc = reads_clear(s); if (rc) return rc; }
+    if (const int rc = passes_clear(s)) return rc;
     if (s->records_on) return records_prepare(s);
     return KVQ_OK;
 }
@@ -223,7 +221,9 @@ static void chain_forget(const kvq_scan *s)
 // timing events are kept for the next scan of the same handle (creating a pair costs several microseconds)
 static void drop_events(kvq_scan *s, bool destroy = false)
 {
-    for (auto *v : { &s->ev_all, &s->ev_main, &s->ev_prof, &s->ev_cyc, &s->ev_reads }) { s->ev_free.insert(s->ev_free.end(), v->begin(), v->end()); v->clear(); }
+    auto keep = [s](std::vector<KvqEventPair> &v) { s->ev_free.insert(s->ev_free.end(), v.begin(), v.end()); v.clear(); };
+    keep(s->ev_all); keep(s->ev_main);
+    for (KvqPass &p : s->passes) keep(p.ev);
     if (destroy) {
         chain_forget(s);
         for (auto &e : s->ev_free) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -245,10 +245,8 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
     if (s->ev_chain) (void)hipEventDestroy(s->ev_chain);
     if (s->pin_rec) pinned_give(s->pin_rec, s->pin_rec_cap);
-    if (s->pin_prof) pinned_give(s->pin_prof, s->pin_prof_cap);
-    if (s->pin_cyc) pinned_give(s->pin_cyc, s->pin_cyc_cap);
-    if (s->pin_reads) pinned_give(s->pin_reads, s->pin_reads_cap);
-    DevBuf *bufs[] = { &s->d_reads, &s->d_dup, &s->d_cyc, &s->d_prof, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
+    for (KvqPass &p : s->passes) { if (p.pin) pinned_give(p.pin, p.pin_cap); p.d.release(); }
+    DevBuf *bufs[] = { &s->d_dup, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
                        &s->d_rec_start, &s->d_read_off, &s->d_read_len, &s->d_arena, &s->d_blob, &s->d_small, &s->d_stage, &s->d_stage_b };
     for (DevBuf *b : bufs) b->release();
     s->pool.release();
@@ -259,13 +257,17 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
 extern "C" int32_t kvq_scan_path(const kvq_scan *s) { return s->path_bits; }
 extern "C" void kvq_scan_force_exhaustive(kvq_scan *s, int32_t on) { s->force_exhaustive = on != 0; }
 
+int scan_idle(const kvq_scan *s, const char *who)
+{
+    if (s->batches.empty() && !s->copied_pending && s->host_pending < 0) return KVQ_OK;
+    kvq_set_error(KVQ_ERR_RUNTIME, "%s: only before the first batch or after kvq_scan_reset", who);
+    return KVQ_ERR_RUNTIME;
+}
+
 extern "C" int32_t kvq_scan_set_records(kvq_scan *s, int32_t on)
 {
     kvq_clear_error();
-    if (!s->batches.empty() || s->copied_pending || s->host_pending >= 0) {
-        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_records: only before the first batch or after kvq_scan_reset");
-        return KVQ_ERR_RUNTIME;
-    }
+    if (const int rc = scan_idle(s, "kvq_scan_set_records")) return rc;
     if (on && s->comm) {
         kvq_set_error(KVQ_ERR_RUNTIME, "records are not gathered across ranks: a scan with a communicator cannot keep them");
         return KVQ_ERR_RUNTIME;
@@ -278,10 +280,7 @@ extern "C" int32_t kvq_scan_set_records(kvq_scan *s, int32_t on)
 extern "C" int32_t kvq_scan_set_long_reads(kvq_scan *s, int32_t mode)
 {
     kvq_clear_error();
-    if (!s->batches.empty() || s->copied_pending || s->host_pending >= 0) {
-        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_long_reads: only before the first batch or after kvq_scan_reset");
-        return KVQ_ERR_RUNTIME;
-    }
+    if (const int rc = scan_idle(s, "kvq_scan_set_long_reads")) return rc;
     if (mode < 0 || mode > 2) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_long_reads: mode must be 0 (off), 1 (on) or 2 (auto)"); return KVQ_ERR_RUNTIME; }
     s->long_mode = mode;
     return KVQ_OK;
@@ -294,7 +293,8 @@ extern "C" int32_t kvq_scan_reset(kvq_scan *s)
     drop_events(s);
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
     s->batches.clear(); s->host_batches = false; s->host_pending = -1; s->copied_pending = false; s->parsed = 0; s->total = 0;
-    s->ms_all = s->ms_main = s->ms_prof = s->ms_cyc = s->ms_reads = 0; s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
+    s->ms_all = s->ms_main = 0; for (KvqPass &p : s->passes) p.ms = 0;
+    s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
     s->tail_pending = false;
     s->pool.used = 0;
     const int rr = reset_device_state(s);
@@ -561,25 +561,21 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
     // the profile: every batch once, by its first pass (the redo of a batch that failed validation leaves it alone, and so does
     // the redo of skipped tiles), from the exact index -- the exhaustive pass's where the batch has one; a seeded batch waits
     // on the host once for its own.  In front of the closing event: what guards the batch's text guards this pass too
-    if (s->profile_on && !exhaustive_only) {
+    // (the cycles and the per-read statistics are on only beside the profile: right behind it, from the same index)
+    if (s->passes[KVQ_PASS_PROFILE].on && !exhaustive_only) {
         if (B.nrec < 0 && (rc = index_records(s, B))) return rc;
-        if (B.nrec > 0) {
-            if ((rc = new_event_pair(s, s->ev_prof))) return rc;
-            KVQ_HIP(hipEventRecord(s->ev_prof.back().first, s->stream));
-            if ((rc = profile_enqueue(s, d_data, (uint64_t)B.nrec))) return rc;
-            KVQ_HIP(hipEventRecord(s->ev_prof.back().second, s->stream));
-            if (s->cycles_on) {                           // right behind it, from the same index
-                if ((rc = new_event_pair(s, s->ev_cyc))) return rc;
-                KVQ_HIP(hipEventRecord(s->ev_cyc.back().first, s->stream));
-                if ((rc = cycles_enqueue(s, d_data, (uint64_t)B.nrec))) return rc;
-                KVQ_HIP(hipEventRecord(s->ev_cyc.back().second, s->stream));
+        for (int i = 0; i < KVQ_PASSES && B.nrec > 0; i++) {
+            KvqPass &p = s->passes[i];
+            if (!p.on) continue;
+            if ((rc = new_event_pair(s, p.ev))) return rc;
+            KVQ_HIP(hipEventRecord(p.ev.back().first, s->stream));
+            switch (i) {
+            case KVQ_PASS_PROFILE: rc = profile_enqueue(s, d_data, (uint64_t)B.nrec); break;
+            case KVQ_PASS_CYCLES: rc = cycles_enqueue(s, d_data, (uint64_t)B.nrec); break;
+            default: rc = reads_enqueue(s, d_data, (uint64_t)B.nrec); break;
             }
-            if (s->reads_mode) {                          // ... and what the single reads look like, from the same index
-                if ((rc = new_event_pair(s, s->ev_reads))) return rc;
-                KVQ_HIP(hipEventRecord(s->ev_reads.back().first, s->stream));
-                if ((rc = reads_enqueue(s, d_data, (uint64_t)B.nrec))) return rc;
-                KVQ_HIP(hipEventRecord(s->ev_reads.back().second, s->stream));
-            }
+            if (rc) return rc;
+            KVQ_HIP(hipEventRecord(p.ev.back().second, s->stream));
         }
     }
     KVQ_HIP(hipEventRecord(s->ev_all.back().second, s->stream));

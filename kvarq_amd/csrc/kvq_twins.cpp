@@ -1,0 +1,131 @@
+// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes (include/kvarq_hip.h, DESIGN sections 13, 14 and 16): the
+// definitions of kvq_profile_records, kvq_profile_cycles and kvq_reads_records in plain C++ (test infrastructure, never a
+// fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record walk serve all three.
+#include "../../include/kvarq_hip.h"
+#include "kvq_dup_hash.h"
+#include <algorithm>
+#include <string.h>
+#include <unordered_map>
+
+void kvq_set_error(int code, const char *fmt, ...);      // (kvq_runtime.hip)
+void kvq_clear_error();
+
+// C from a wish: the default, or what the wish shrinks it to -- no less than KVQ_DUP_MIN_SLOTS, rounded down to a power of two
+// (kvq_scan_set_read_stats sizes the device's tables with it)
+static uint64_t dup_slots_from(long long wish)
+{
+    if (wish <= 0 || wish >= KVQ_DUP_DEFAULT_SLOTS) return KVQ_DUP_DEFAULT_SLOTS;
+    uint64_t c = KVQ_DUP_MIN_SLOTS;
+    while (2 * c <= (uint64_t)wish) c *= 2;
+    return c;
+}
+
+// what every twin asks of its text and chunk table (`ok`: what it asks beyond that)
+static bool twin_args(const char *who, bool ok, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks)
+{
+    kvq_clear_error();
+    ok = ok && nbytes >= 0 && nchunks >= 0 && (nchunks == 0 || chunk_off);
+    for (int64_t c = 0; ok && c <= nchunks && nchunks > 0; c++) ok = chunk_off[c] >= 0 && chunk_off[c] <= nbytes && (!c || chunk_off[c] >= chunk_off[c - 1]);
+    if (!ok) kvq_set_error(KVQ_ERR_RUNTIME, "%s: bad arguments", who);
+    return ok;
+}
+
+// every four newlines of a chunk are a record: fn(n0, n1, n2, n3), their offsets (an incomplete tail of a chunk is no record)
+template <class F> static void for_each_record(const uint8_t *text, const int64_t *chunk_off, int64_t nchunks, F fn)
+{
+    for (int64_t c = 0; c < nchunks; c++) {
+        int64_t nl[4]; int have = 0;
+        for (int64_t i = chunk_off[c]; i < chunk_off[c + 1]; i++) {
+            if (text[i] != '\n') continue;
+            nl[have++] = i;
+            if (have == 4) { have = 0; fn(nl[0], nl[1], nl[2], nl[3]); }
+        }
+    }
+}
+
+extern "C" uint64_t kvq_dup_hash_host(const uint8_t *line, int64_t L) { return line && L > 0 ? kvq_dup_hash(line, (uint64_t)L) : 0; }
+
+extern "C" int32_t kvq_reads_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t slots,
+                                  int64_t *reads_out, int64_t *dup_out)
+{
+    if (!twin_args("kvq_reads_host", true, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    std::unordered_map<uint64_t, int64_t> keys;                                // every key of the input with its count
+    int64_t keyed = 0, unkeyed = 0;
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
+        const uint8_t *bases = text + n0 + 1, *scores = text + n2 + 1;
+        int64_t L = n1 - n0 - 1, Q = n3 - n2 - 1;
+        if (L > 0 && bases[L - 1] == '\r') L--;                                // a trailing '\r' is not part of its line
+        if (Q > 0 && scores[Q - 1] == '\r') Q--;
+        if (reads_out) {
+            int64_t a = 0, g = 0, n = 0, S = 0;
+            for (int64_t j = 0; j < L; j++) {
+                const uint8_t b = bases[j];
+                a += b == 'A' || b == 'C' || b == 'G' || b == 'T'; g += b == 'G' || b == 'C'; n += b == 'N';
+            }
+            for (int64_t j = 0; j < Q; j++) S += scores[j];
+            reads_out[KVQ_READS_RECORDS]++;
+            if (a > 0) reads_out[KVQ_READS_GC + (200 * g + a) / (2 * a)]++; else reads_out[KVQ_READS_GC_NONE]++;
+            if (Q > 0) reads_out[KVQ_READS_MEANQ + (2 * S + Q) / (2 * Q)]++; else reads_out[KVQ_READS_MEANQ_NONE]++;
+            reads_out[KVQ_READS_NCOUNT + std::min<int64_t>(n, 255)]++;
+        }
+        if (dup_out) {
+            if (L == 0) unkeyed++;
+            else { keyed++; keys[kvq_dup_hash(bases, (uint64_t)L)]++; }
+        }
+    });
+    if (!dup_out) return KVQ_OK;
+    const uint64_t C = dup_slots_from(slots);
+    uint32_t level = 0;
+    for (;; level++) {                                                          // the smallest level with at most C / 2 distinct tracked keys
+        uint64_t tracked = 0;
+        for (const auto &k : keys) tracked += kvq_dup_tracked(k.first, level);
+        if (tracked <= C / 2) break;
+    }
+    memset(dup_out, 0, (size_t)KVQ_DUP_WORDS * 8);
+    dup_out[KVQ_DUP_LEVEL] = level; dup_out[KVQ_DUP_SLOTS] = (int64_t)C; dup_out[KVQ_DUP_KEYED] = keyed; dup_out[KVQ_DUP_UNKEYED] = unkeyed;
+    for (const auto &k : keys) {
+        if (!kvq_dup_tracked(k.first, level)) continue;
+        const uint32_t b = kvq_dup_bin((uint64_t)k.second);
+        dup_out[KVQ_DUP_DISTINCT + b]++; dup_out[KVQ_DUP_RECORDS + b] += k.second;
+        dup_out[KVQ_DUP_TRACKED_KEYS]++; dup_out[KVQ_DUP_TRACKED_RECORDS] += k.second;
+    }
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_cycles_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t *out)
+{
+    if (!twin_args("kvq_cycles_host", out != nullptr, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    int64_t *const score = out, *const base = out + (int64_t)KVQ_CYCLES * 256;
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
+        for (int64_t p = 0; p < KVQ_CYCLES && n0 + 1 + p < n1; p++) base[p * 256 + text[n0 + 1 + p]]++;
+        for (int64_t p = 0; p < KVQ_CYCLES && n2 + 1 + p < n3; p++) score[p * 256 + text[n2 + 1 + p]]++;
+    });
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_profile_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                    const uint8_t *cutoffs, int32_t ncut, int64_t *out)
+{
+    if (!twin_args("kvq_profile_host", out && ncut >= 0 && ncut <= KVQ_PROFILE_MAX_CUTOFFS && (ncut == 0 || cutoffs), nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
+        const int64_t L = n1 - n0 - 1, Q = n3 - n2 - 1;
+        out[KVQ_PROF_RECORDS]++; out[KVQ_PROF_BASE_LINE_BYTES] += L; out[KVQ_PROF_SCORE_LINE_BYTES] += Q; out[KVQ_PROF_MISMATCHED] += L != Q;
+        out[KVQ_PROF_LONGEST] = std::max(out[KVQ_PROF_LONGEST], L + 1);
+        out[KVQ_PROF_RAW_LENGTHS + std::min<int64_t>(L, KVQ_PROF_RAW_BINS - 1)]++;
+        for (int64_t i = n0 + 1; i < n1; i++) out[KVQ_PROF_BASE_BYTES + text[i]]++;
+        for (int64_t i = n2 + 1; i < n3; i++) out[KVQ_PROF_SCORE_BYTES + text[i]]++;
+        for (int k = 0; k < ncut; k++) {
+            // workhorse.c:1055-1068 over the score line and its newline
+            const int amin = (int8_t)cutoffs[k];
+            int64_t run = n2 + 1, best = 0;
+            for (int64_t i = n2 + 1; i <= n3; i++) {
+                if ((int)(int8_t)text[i] >= amin) { if (run < 0) run = i; }
+                else { if (run >= 0 && i - run > best) best = i - run; run = -1; }
+            }
+            int64_t *const cut = out + KVQ_PROF_CUTOFFS + (int64_t)k * KVQ_PROF_CUT_WORDS;
+            if (best < KVQ_MAX_READLENGTH) cut[1 + best]++;                 // add_rl, workhorse.c:394-402
+            if (best + 1 > cut[0]) cut[0] = best + 1;
+        }
+    });
+    return KVQ_OK;
+}

@@ -20,6 +20,7 @@ import ctypes as C
 from . import _lib
 from .fastq import FastqFileFormatException
 from .log import lo
+from .options import ScanOptions
 
 # workhorse.c:1579-1596
 Hit = collections.namedtuple('Hit', 'seq_nr file_pos seq_pos length readlength')
@@ -105,15 +106,60 @@ def _stats_dict(readlengths, longest, nseqbasehits, nseqhits, parsed, total, sig
     }
 
 
+# ---- a finished scan object as Python objects: the one reader of its arrays (findseqs below, scan.Scanner) ----
+def scan_arrays(L, h):
+    """views of the library's result arrays: the five columns of ``Hit``, 'offsets' (n + 1, into the hit bytes), and the
+    hit bytes themselves, 'blob' (``bytes``); valid until the scan object is reset or destroyed"""
+    nh = L.kvq_scan_n_hits(h)
+    a = {'seq_nr': _lib.view(L.kvq_scan_hit_seq_nr(h), nh, C.c_int32, np.int32), 'file_pos': _lib.view(L.kvq_scan_hit_file_pos(h), nh, C.c_int64, np.int64),
+         'seq_pos': _lib.view(L.kvq_scan_hit_seq_pos(h), nh, C.c_int32, np.int32), 'length': _lib.view(L.kvq_scan_hit_length(h), nh, C.c_int32, np.int32),
+         'readlength': _lib.view(L.kvq_scan_hit_readlength(h), nh, C.c_int32, np.int32),
+         'offsets': _lib.view(L.kvq_scan_hitseq_offsets(h), nh + 1, C.c_int64, np.int64)}
+    a['blob'] = C.string_at(L.kvq_scan_hitseq_blob(h), int(a['offsets'][nh])) if nh else b''
+    return a
+
+
+def scan_hits(L, h, as_str=False):
+    """-> (the reference's ``hits`` tuple, its ``hitseqs`` list: ``bytes``, or ``str`` via latin-1)"""
+    a = scan_arrays(L, h)
+    # (the arrays become Python objects in bulk: one ctypes index operation per field of every hit cost more than the scan of a
+    # 3 GB file; tuple.__new__(Hit, fields) is what Hit(*fields) ends up calling, without the Python-level frame in between)
+    hits = tuple(map(tuple.__new__, itertools.repeat(Hit), zip(*(a[f].tolist() for f in Hit._fields))))
+    off, blob = a['offsets'].tolist(), a['blob'].decode('latin-1') if as_str else a['blob']
+    return hits, [blob[x:y] for x, y in zip(off, off[1:])]
+
+
+def scan_records(L, h, as_str=False):
+    """the records of a finished scan object's hits, in the order of ``hits`` (kvq_scan_hit_record_off / _len into kvq_scan_record_blob)"""
+    nh = L.kvq_scan_n_hits(h)
+    if not nh:
+        return []
+    off = _lib.view(L.kvq_scan_hit_record_off(h), nh, C.c_int64, np.int64).tolist()
+    ln = _lib.view(L.kvq_scan_hit_record_len(h), nh, C.c_int32, np.int32).tolist()
+    blob = C.string_at(L.kvq_scan_record_blob(h), L.kvq_scan_record_bytes(h))
+    if as_str:
+        blob = blob.decode('latin-1')
+    return [blob[a:a + b] for a, b in zip(off, ln)]
+
+
+def scan_stats(L, h, nseq, sigints, ctr=None):
+    """the ``stats`` dict of a finished scan object over ``nseq`` sequences (``ctr``: its counters, where the caller has them)"""
+    # counters layout (include/kvarq_hip.h): 4 scalars, readlengths[1024], nseqhits[n], nseqbasehits[n], ...
+    o_hits = _lib.CTR_READLENGTHS + _lib.MAX_READLENGTH
+    if ctr is None:
+        ctr = _lib.view(L.kvq_scan_counters(h), o_hits + 2 * nseq, C.c_int64, np.int64)
+    ctr = ctr[:o_hits + 2 * nseq].tolist()
+    return _stats_dict(ctr[_lib.CTR_READLENGTHS:o_hits], ctr[_lib.CTR_LONGEST] - 1, ctr[o_hits + nseq:o_hits + 2 * nseq], ctr[o_hits:o_hits + nseq],
+                       L.kvq_scan_parsed(h), L.kvq_scan_total(h), sigints, ctr[_lib.CTR_RECORDS])
+
+
 _last_inflate = None
 _last_long_reads = None
 INFLATE_FLAGS = {'host': 0, 'device': 1, 'device_any': 2}     # KVQ_FIND_DEVICE_INFLATE, KVQ_FIND_DEVICE_GZIP
-PATH_DEVICE_INFLATE = 0x10                         # kvq_scan_path bit 4
-PATH_DEVICE_GZIP = 0x20                            # kvq_scan_path bit 5
-PATH_DEVICE_BAM = 0x40                             # kvq_scan_path bit 6
+PATH_DEVICE_INFLATE, PATH_DEVICE_GZIP, PATH_DEVICE_BAM = _lib.PATH_DEVICE_INFLATE, _lib.PATH_DEVICE_GZIP, _lib.PATH_DEVICE_BAM
 
 
-def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False):
+def findseqs(fname, sequences, *, inflate='host', **options):
     """findseqs(fname, sequences) -- finds occurences of base sequences in fastq files
     (workhorse.c:1249-1464).
 
@@ -165,7 +211,7 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
     has no seed index the option changes nothing.  last_long_reads() tells whether the route ran."""
     import os, time
     global _last_inflate, _last_long_reads
-    long_flag = (0, _lib.FIND_LONG_READS, _lib.FIND_LONG_READS_AUTO)[_lib.long_reads_mode(long_reads)]
+    opt = ScanOptions(**options)
     if inflate not in INFLATE_FLAGS:
         raise ValueError("inflate must be 'host', 'device' or 'device_any'")
     _last_inflate = _last_long_reads = None
@@ -204,19 +250,7 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
-    if (cycles or per_read or duplication) and profile is None:
-        profile = ()
-    if profile is not None:
-        from . import profile as profile_
-        cuts = profile_.as_cutoffs(profile)
-        opts = _lib.FindOpts(C.sizeof(_lib.FindOpts), INFLATE_FLAGS[inflate] | long_flag | (_lib.FIND_RECORDS if records else 0) | _lib.FIND_PROFILE |
-                             (_lib.FIND_CYCLES if cycles else 0) | (_lib.FIND_READ_STATS if per_read else 0) | (_lib.FIND_DUPLICATION if duplication else 0),
-                             len(cuts), (C.c_uint8 * 8)(*cuts))
-        h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opts))
-    elif inflate == 'host' and not records and not long_flag:
-        h = L.kvq_findseqs(farr, len(bfiles), sarr, lens, n)
-    else:
-        h = L.kvq_findseqs_ex(farr, len(bfiles), sarr, lens, n, INFLATE_FLAGS[inflate] | long_flag | (_lib.FIND_RECORDS if records else 0))
+    h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opt.find_opts(INFLATE_FLAGS[inflate])))
     t_1 = time.perf_counter()
     try:
         if h:
@@ -227,27 +261,8 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
         code, _ = _lib.last_error()
         if not h or code:
             _raise_last()
-        nh = L.kvq_scan_n_hits(h)
-        # (the arrays become Python objects in bulk: one ctypes index operation per field of every hit cost more
-        # than the scan of a 3 GB file)
-        def col(ptr, count):
-            return np.ctypeslib.as_array(ptr, shape=(count,)).tolist() if count else []
-        # (tuple.__new__(Hit, fields) is what Hit(*fields) ends up calling, without the Python-level frame in between)
-        hits = tuple(map(tuple.__new__, itertools.repeat(Hit),
-                         zip(col(L.kvq_scan_hit_seq_nr(h), nh), col(L.kvq_scan_hit_file_pos(h), nh), col(L.kvq_scan_hit_seq_pos(h), nh),
-                             col(L.kvq_scan_hit_length(h), nh), col(L.kvq_scan_hit_readlength(h), nh))))
-        off = col(L.kvq_scan_hitseq_offsets(h), nh + 1)
-        blob = C.string_at(L.kvq_scan_hitseq_blob(h), off[nh]) if nh else b''
-        if as_str:
-            blob = blob.decode('latin-1')
-        hitseqs = [blob[a:b] for a, b in zip(off, off[1:])]
-        # counters layout (include/kvarq_hip.h): 4 scalars, readlengths[1024], nseqhits[n], nseqbasehits[n], ...
-        o_hits = _lib.CTR_READLENGTHS + _lib.MAX_READLENGTH
-        ctr = col(L.kvq_scan_counters(h), o_hits + 2 * n)
-        st = _stats_dict(
-            ctr[_lib.CTR_READLENGTHS:o_hits], ctr[_lib.CTR_LONGEST] - 1,
-            ctr[o_hits + n:o_hits + 2 * n], ctr[o_hits:o_hits + n],
-            L.kvq_scan_parsed(h), L.kvq_scan_total(h), _sigints(), ctr[_lib.CTR_RECORDS])
+        hits, hitseqs = scan_hits(L, h, as_str)
+        st = scan_stats(L, h, n, _sigints())
         if os.environ.get('KVQ_TIMING'):
             import sys
             sys.stderr.write('engine.findseqs: arguments %.1f ms, library %.1f ms, results as Python objects %.1f ms\n' % ((t_0 - t_in) * 1e3, (t_1 - t_0) * 1e3, (time.perf_counter() - t_1) * 1e3))
@@ -257,9 +272,10 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
             if noqual:
                 lo.warning('%d BAM records without qualities were written with Phred 1 (\'"\'): at the default Amin '
                            'they are trimmed to nothing' % noqual)
-        if records:
-            out['records'] = _records(L, h, nh, as_str)
-        if profile is not None:
+        if opt.records:
+            out['records'] = scan_records(L, h, as_str)
+        if opt.profile is not None:
+            from . import profile as profile_
             out['profile'] = profile_.from_scan(L, h)
         return out
     finally:
@@ -269,18 +285,6 @@ def findseqs(fname, sequences, *, inflate='host', records=False, profile=None, c
             if os.environ.get('KVQ_TIMING'):
                 import sys
                 sys.stderr.write('engine.findseqs: free %.1f ms\n' % ((time.perf_counter() - t_f) * 1e3))
-
-
-def _records(L, h, nh, as_str):
-    """the records of a finished scan object's hits (kvq_scan_hit_record_off / _len into kvq_scan_record_blob)"""
-    if not nh:
-        return []
-    off = np.ctypeslib.as_array(L.kvq_scan_hit_record_off(h), shape=(nh,)).tolist()
-    ln = np.ctypeslib.as_array(L.kvq_scan_hit_record_len(h), shape=(nh,)).tolist()
-    blob = C.string_at(L.kvq_scan_record_blob(h), L.kvq_scan_record_bytes(h))
-    if as_str:
-        blob = blob.decode('latin-1')
-    return [blob[a:a + b] for a, b in zip(off, ln)]
 
 
 def last_inflate():

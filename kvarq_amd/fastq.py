@@ -292,13 +292,12 @@ class Fastq(object):
             at += length
         return best
 
-    def profile(self, cutoffs=None, inflate='host', cycles=False, long_reads=False, per_read=False, duplication=False):
+    def profile(self, cutoffs=None, inflate='host', **options):
         """the exact answer to what the constructor guesses from a sample: a ``kvarq_amd.profile.Profile`` of every
         record of the file (and its mate), taken on the GPU; cutoffs None: the configured Amin; ``cycles``: with the
-        per-cycle counts"""
+        per-cycle counts (``options``: as for ``kvarq_amd.profile.profile``)"""
         from . import profile as profile_
-        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs, inflate=inflate, cycles=cycles, long_reads=long_reads,
-                                per_read=per_read, duplication=duplication)
+        return profile_.profile(self.filenames(), True if cutoffs is None else cutoffs, inflate=inflate, **options)
 
     # -- PHRED arithmetic ------------------------------------------------------------------------------
 

@@ -1,0 +1,49 @@
+"""
+The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
+``duplication`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
+"""
+import ctypes as C
+
+from . import _lib
+
+
+class ScanOptions(object):
+    """``records``: keep the FastQ record of every hit; ``profile``: the cutoffs of the input's profile
+    (``profile.as_cutoffs``; True: ``amin``, or the configured Amin; None: no profile) -- a list of byte values here;
+    ``cycles``: the per-cycle counts beside it; ``read_stats``: the mode bits of kvq_scan_set_read_stats for ``per_read`` and
+    ``duplication``; ``long_mode``: the mode of kvq_scan_set_long_reads for ``long_reads`` (False, True or 'auto').
+    ``cycles``, ``per_read`` or ``duplication`` without ``profile`` mean a profile with no cutoffs."""
+
+    def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, amin=None):
+        self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
+        self.records, self.cycles = bool(records), bool(cycles)
+        self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
+        if (self.cycles or self.read_stats) and profile is None:
+            profile = ()
+        self.profile = None
+        if profile is not None:
+            from .profile import as_cutoffs
+            self.profile = as_cutoffs(profile, amin=amin)
+
+    def find_opts(self, flags=0):
+        """the kvq_find_opts of kvq_findseqs_opts (``flags``: the caller's own, OR-ed in)"""
+        flags |= (0, _lib.FIND_LONG_READS, _lib.FIND_LONG_READS_AUTO)[self.long_mode] | (_lib.FIND_RECORDS if self.records else 0)
+        if self.profile is not None:
+            flags |= (_lib.FIND_PROFILE | (_lib.FIND_CYCLES if self.cycles else 0) | (_lib.FIND_READ_STATS if self.read_stats & _lib.READ_STATS else 0) |
+                      (_lib.FIND_DUPLICATION if self.read_stats & _lib.READ_DUPLICATION else 0))
+        cuts = self.profile or ()
+        return _lib.FindOpts(C.sizeof(_lib.FindOpts), flags, len(cuts), (C.c_uint8 * 8)(*cuts))
+
+    def setters(self):
+        """the kvq_scan_set_* calls of a new scan handle, in order: (name, arguments behind the handle)"""
+        calls = [('kvq_scan_set_records', (1,))] if self.records else []
+        if self.profile is not None:
+            calls.append(('kvq_scan_set_profile', ((C.c_uint8 * 8)(*self.profile), len(self.profile))))
+            if self.cycles:
+                calls.append(('kvq_scan_set_cycles', (1,)))
+            if self.read_stats:
+                calls.append(('kvq_scan_set_read_stats', (self.read_stats,)))
+        if self.long_mode:
+            calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
+        return calls

@@ -453,12 +453,12 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False,
     return Profile(out, cuts, cyc, reads, dup)
 
 
-def profile(fnames, cutoffs=True, inflate='host', cycles=False, long_reads=False, per_read=False, duplication=False):
+def profile(fnames, cutoffs=True, inflate='host', **options):
     """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
-    per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication"""
+    per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication; ``long_reads``:
+    as for ``engine.findseqs``, which takes the ``options``"""
     from . import engine
-    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, cycles=cycles, long_reads=long_reads,
-                           per_read=per_read, duplication=duplication)['profile']
+    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)['profile']
 
 
 def main(argv=None):
@@ -473,11 +473,11 @@ def main(argv=None):
     ap.add_argument('--per-read', action='store_true', help='the per-read GC histogram in 5 %% steps with its mean, the quantiles of the per-read mean quality, the share of reads with any N')
     ap.add_argument('--duplication', action='store_true', help='how often the first 64 bases of the reads repeat: level, sample size and a line per count bin')
     a = ap.parse_args(argv)
-    more = dict(per_read=a.per_read, duplication=a.duplication)
-    p = profile(a.files, cutoffs=True, inflate=a.inflate, cycles=a.cycles and not a.quality, **({} if a.quality else more))
+    more = dict(cycles=a.cycles, per_read=a.per_read, duplication=a.duplication)
+    p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
-        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate, cycles=a.cycles, **more)
+        p = profile(a.files, cutoffs=[ASCII[q + dQ] for q in a.quality], inflate=a.inflate, **more)
     print(p.summary())
     if a.cycles:
         print('\n'.join(p.cycle_lines(a.cycle_step)))

@@ -11,7 +11,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .engine import Hit, _raise_last
+from ._lib import view as _view
+from .engine import Hit, _raise_last, scan_arrays, scan_hits, scan_records, scan_stats
+from .options import ScanOptions
 
 
 def _check(rc):
@@ -75,14 +77,6 @@ def chunk_offsets(data):
     return np.array(list(out)[:n + 1], dtype=np.int64)
 
 
-def _view(ptr, n, ctype, dtype):
-    """numpy view of a C array the library owns (np.ctypeslib.as_array costs ~60 us per call)"""
-    addr = C.cast(ptr, C.c_void_p).value
-    if not addr or n <= 0:
-        return np.zeros(0, dtype=dtype)
-    return np.frombuffer((ctype * n).from_address(addr), dtype=dtype)
-
-
 class RescanRequired(RuntimeError):
     """the hit arena overflowed on host batches that the Scanner no longer holds: reset() and feed them again"""
 
@@ -96,34 +90,17 @@ class Scanner(object):
     ``finish`` raises ``RescanRequired`` and the caller, who has the data, resets and feeds again; a caller with
     a re-readable source passes ``replay=callable`` (called with the scanner after ``reset()``) instead."""
 
-    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False):
+    def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, **options):
         self.table = table
-        long_mode = _lib.long_reads_mode(long_reads)
+        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication (``options.ScanOptions``), set on the
+        # scan handle once and kept across reset
+        opt = ScanOptions(amin=bytes([table.config.Amin & 0xFF]), **options)
+        self.records, self.profile, self.cycles, self.read_stats, self.long_reads = opt.records, opt.profile, opt.cycles, opt.read_stats, opt.long_reads
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
-        self.records = bool(records)     # keep the FastQ record of every hit (kvq_scan_set_records; kept across reset)
-        if self.records:
-            _check(_lib.lib().kvq_scan_set_records(self.h, 1))
-        # profile the input at these cutoffs (kvarq_amd.profile.as_cutoffs; True: the table's Amin); kept across reset
-        # cycles: the per-cycle counts beside the profile (kvq_scan_set_cycles); without ``profile``: a profile with no cutoffs
-        # per_read / duplication: the per-read distributions / the duplication beside it (kvq_scan_set_read_stats), in the same way
-        self.profile, self.cycles = None, bool(cycles)
-        self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
-        if (self.cycles or self.read_stats) and profile is None:
-            profile = ()
-        if profile is not None:
-            from . import profile as profile_
-            self.profile = profile_.as_cutoffs(profile, amin=bytes([table.config.Amin & 0xFF]))
-            _check(_lib.lib().kvq_scan_set_profile(self.h, (C.c_uint8 * 8)(*self.profile), len(self.profile)))
-            if self.cycles:
-                _check(_lib.lib().kvq_scan_set_cycles(self.h, 1))
-            if self.read_stats:
-                _check(_lib.lib().kvq_scan_set_read_stats(self.h, self.read_stats))
-        # the read-list route for reads of thousands of bases (kvq_scan_set_long_reads; True, or 'auto': by each batch's head); kept across reset
-        self.long_reads = long_reads
-        if long_mode:
-            _check(_lib.lib().kvq_scan_set_long_reads(self.h, long_mode))
+        for name, args in opt.setters():
+            _check(getattr(_lib.lib(), name)(self.h, *args))
         self._host_batches = []          # copies of what scan_host was given since the last reset (fed again when the hit arena overflows)
         self._device_batches = []        # what scan_device was given since the last reset (the caller's device memory: nothing is copied)
         self._retained, self._retain_limit, self._replay = 0, (0 if replay is not None else retain_limit), replay
@@ -207,7 +184,7 @@ class Scanner(object):
         if hits:
             out.update(self._hits_dict())
             if self.records:
-                out['records'] = self._records()
+                out['records'] = scan_records(L, self.h)      # the record of every hit (bytes), in the order of ``hits``
         if self.profile is not None:
             from . import profile as profile_
             out['profile'] = profile_.from_scan(L, self.h)
@@ -221,20 +198,12 @@ class Scanner(object):
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
         if not stats:
             return out
-        longest = int(ctr[_lib.CTR_LONGEST]) - 1
-        parsed, total = L.kvq_scan_parsed(self.h), L.kvq_scan_total(self.h)
-        rls = ctr[_lib.CTR_READLENGTHS:_lib.CTR_READLENGTHS + _lib.MAX_READLENGTH]
-        out['stats'] = {
-            'readlengths': tuple(int(rls[i]) if i < _lib.MAX_READLENGTH else 0 for i in range(longest + 1)),
-            'progress': (C.c_float(C.c_float(min(parsed, total)).value / C.c_float(total).value).value if total > 0 else 0.0),
-            'nseqbasehits': tuple(int(x) for x in ctr[t.off_nseqbasehits:t.off_nseqbasehits + t.nseq]),
-            'nseqhits': tuple(int(x) for x in ctr[t.off_nseqhits:t.off_nseqhits + t.nseq]),
-            'parsed': parsed, 'total': total, 'sigints': 0, 'records_parsed': int(ctr[_lib.CTR_RECORDS]),
-        }
+        out['stats'] = scan_stats(L, self.h, t.nseq, 0, ctr)
         out['coverage'] = ctr[t.off_coverage:t.off_coverage + t.bases]
         out['mutations'] = ctr[t.off_mutations:t.off_mutations + 6 * t.bases]
         path = L.kvq_scan_path(self.h)
-        out['path'] = {'seeded': bool(path & 1), 'exhaustive': bool(path & 2), 'rescanned': bool(path & 4), 'tiles_rescanned': bool(path & 8)}
+        out['path'] = {'seeded': bool(path & _lib.PATH_SEEDED), 'exhaustive': bool(path & _lib.PATH_EXHAUSTIVE),
+                       'rescanned': bool(path & _lib.PATH_RESCANNED), 'tiles_rescanned': bool(path & _lib.PATH_TILES_RESCANNED)}
         if self.long_reads is not False:
             out['path']['read_list'] = bool(path & _lib.PATH_READ_LIST)      # a batch took the read-list route
         out['kernel'] = _lib.kernel_cell(L.kvq_scan_kernel(self.h))      # the scan kernel instantiation of the last seed-filter launch
@@ -263,14 +232,8 @@ class Scanner(object):
         """the library's result arrays as numpy arrays (copies): seq_nr, file_pos, seq_pos, length, readlength,
         hitseq offsets (n + 1), hit bytes"""
         L = _lib.lib()
-        nh = L.kvq_scan_n_hits(self.h)
-        a = [_view(f(self.h), nh, ct, dt).copy()
-             for f, ct, dt in ((L.kvq_scan_hit_seq_nr, C.c_int32, np.int32), (L.kvq_scan_hit_file_pos, C.c_int64, np.int64),
-                               (L.kvq_scan_hit_seq_pos, C.c_int32, np.int32), (L.kvq_scan_hit_length, C.c_int32, np.int32),
-                               (L.kvq_scan_hit_readlength, C.c_int32, np.int32))]
-        off = _view(L.kvq_scan_hitseq_offsets(self.h), nh + 1, C.c_int64, np.int64).copy()
-        blob = np.frombuffer(C.string_at(L.kvq_scan_hitseq_blob(self.h), int(off[nh])) if nh else b'', dtype=np.uint8)
-        out = dict(seq_nr=a[0], file_pos=a[1], seq_pos=a[2], length=a[3], readlength=a[4], offsets=off, blob=blob)
+        out = {k: np.frombuffer(v, dtype=np.uint8) if k == 'blob' else v.copy() for k, v in scan_arrays(L, self.h).items()}
+        nh = len(out['seq_nr'])
         if self.records:
             # hit i's record: record_blob[record_off[i] : record_off[i] + record_len[i]]
             out['record_off'] = _view(L.kvq_scan_hit_record_off(self.h), nh, C.c_int64, np.int64).copy()
@@ -279,29 +242,10 @@ class Scanner(object):
             out['record_blob'] = np.frombuffer(C.string_at(L.kvq_scan_record_blob(self.h), nb) if nb else b'', dtype=np.uint8)
         return out
 
-    def _records(self):
-        """the record of every hit (bytes), in the order of ``hits``"""
-        L = _lib.lib()
-        nh = L.kvq_scan_n_hits(self.h)
-        if not nh:
-            return []
-        off = _view(L.kvq_scan_hit_record_off(self.h), nh, C.c_int64, np.int64).tolist()
-        ln = _view(L.kvq_scan_hit_record_len(self.h), nh, C.c_int32, np.int32).tolist()
-        blob = C.string_at(L.kvq_scan_record_blob(self.h), L.kvq_scan_record_bytes(self.h))
-        return [blob[a:a + b] for a, b in zip(off, ln)]
-
     def _hits_dict(self):
-        """the library's result arrays as the reference's ``hits`` tuple and ``hitseqs`` list"""
-        L = _lib.lib()
-        nh = L.kvq_scan_n_hits(self.h)
-        a = [_view(f(self.h), nh, ct, dt).copy()
-             for f, ct, dt in ((L.kvq_scan_hit_seq_nr, C.c_int32, np.int32), (L.kvq_scan_hit_file_pos, C.c_int64, np.int64),
-                               (L.kvq_scan_hit_seq_pos, C.c_int32, np.int32), (L.kvq_scan_hit_length, C.c_int32, np.int32),
-                               (L.kvq_scan_hit_readlength, C.c_int32, np.int32))]
-        hits = tuple(Hit(int(a[0][i]), int(a[1][i]), int(a[2][i]), int(a[3][i]), int(a[4][i])) for i in range(nh))
-        off = L.kvq_scan_hitseq_offsets(self.h)
-        blob = C.string_at(L.kvq_scan_hitseq_blob(self.h), off[nh]) if nh else b''
-        return {'n_hits': nh, 'hits': hits, 'hitseqs': [blob[off[i]:off[i + 1]] for i in range(nh)]}
+        """the library's result arrays as the reference's ``hits`` tuple and ``hitseqs`` list (bytes)"""
+        hits, hitseqs = scan_hits(_lib.lib(), self.h)
+        return {'n_hits': len(hits), 'hits': hits, 'hitseqs': hitseqs}
 
     def reset(self):
         self._host_batches, self._device_batches, self._retained = [], [], 0
