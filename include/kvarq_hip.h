@@ -333,6 +333,49 @@ int32_t        kvq_reads_host(const uint8_t *text, int64_t nbytes, const int64_t
                               int64_t *reads_out, int64_t *dup_out);
 uint64_t       kvq_dup_hash_host(const uint8_t *line, int64_t L);
 
+/* ---- overrepresented sequences: WHICH SEQUENCES THE DUPLICATES ARE ----
+ * Records, lines, key and hash are those of the duplication above: the profile's record set, a trailing '\r' is not part of its
+ * line, the KEY is the first n = min(L, 64) bytes of the bases line, a record with L == 0 is "unkeyed", the hash is kvq_dup_hash.
+ * Two keys with equal hashes are one key (the bytes kept are then those of whichever came first to its slot of the table: a
+ * 2^-64 event per pair of keys).
+ * The scan's records are numbered from 0 in the order its batches are fed, and within a batch in text order.  The CANDIDATES
+ * are the distinct keys of the keyed records with a number < M, M = KVQ_OVER_DEFAULT_RECORDS = 2^18 (KVQ_OVER_RECORDS=<n> in the
+ * environment, read when the option is turned on and clamped to KVQ_OVER_MIN_RECORDS .. KVQ_OVER_MAX_RECORDS: the tests' hook).
+ * Every candidate's COUNT is the number of records OF THE WHOLE INPUT with its key; records whose key is no candidate count
+ * nowhere but in `keyed`.  The result does not depend on batch cuts, slices, launches or rescans.  A candidate is LISTED when
+ * count >= 2 and 1000 * count >= keyed (in integers; keyed: of the whole input): a share of 0.1 % and more.  Counts sum to at
+ * most keyed, so at most KVQ_OVER_MAX_ROWS = 1000 candidates are listed -- a consequence, not a cut-off.
+ * THE LIMIT: a sequence that is not among the first M records is not found, whatever its share.  In a file that is not sorted a
+ * sequence with a share of 0.1 % is missing from the first 2^18 records with probability (1 - 0.001)^(2^18) = e^-262; a file
+ * sorted by sequence or by position can hide one.
+ * The result: one flat int64 array of kvq_over_len() = 8 + 1000 * 11 words:
+ *   [0] M     [1] slots of the table: 4 * (M rounded up to a power of two), at least 1024     [2] keyed records
+ *   [3] unkeyed records     [4] candidates     [5] records counted on candidates (the sum of the counts)     [6] listed rows
+ *   [7] 0
+ *   [8 + 11 r .. +11), r < [6]: row r = {hash, count, n, w0 .. w7}, the key zero-padded to 64 bytes as eight little-endian words;
+ *   zeros behind the last row.  The rows are in canonical order: count descending, ties by hash ascending AS UNSIGNED.
+ *   [2] + [3] == the profile's records, [5] <= [2], [5] == [2] when the input has at most M records.
+ * kvq_scan_set_overrepresented: on != 0 turns the pass on, 0 off; rules as for kvq_scan_set_cycles: before the first batch or after
+ * kvq_scan_reset, KVQ_ERR_RUNTIME when the scan keeps no profile, off together with it, none with a communicator.  Every batch is
+ * then counted once, behind its other passes; wherever the profile is cleared the table is, and the numbering starts at 0 again.
+ * kvq_scan_over: the array (valid after kvq_scan_finish until the next reset), NULL when the option is off.  The table (88 bytes a
+ * slot: 92 MB at the default M) and the landing buffer exist only while the option is on; off, nothing is enqueued or allocated. */
+enum { KVQ_OVER_M = 0, KVQ_OVER_SLOTS = 1, KVQ_OVER_KEYED = 2, KVQ_OVER_UNKEYED = 3, KVQ_OVER_CANDIDATES = 4, KVQ_OVER_COUNTED = 5,
+       KVQ_OVER_LISTED = 6, KVQ_OVER_ROWS = 8, KVQ_OVER_ROW_WORDS = 11, KVQ_OVER_ROW_HASH = 0, KVQ_OVER_ROW_COUNT = 1, KVQ_OVER_ROW_N = 2,
+       KVQ_OVER_ROW_KEY = 3, KVQ_OVER_MAX_ROWS = 1000, KVQ_OVER_WORDS = 8 + 1000 * 11 };
+#define KVQ_OVER_DEFAULT_RECORDS (1 << 18)
+#define KVQ_OVER_MIN_RECORDS 16
+#define KVQ_OVER_MAX_RECORDS (1 << 22)
+int64_t        kvq_over_len(void);
+int32_t        kvq_scan_set_overrepresented(kvq_scan *s, int32_t on);
+const int64_t *kvq_scan_over(const kvq_scan *s);
+/* host only, plain C++: the CPU twin of kvq_over_records and kvq_over_select over the same definition -- test infrastructure and
+ * the definition in running code, not a fallback.  Arguments as for kvq_profile_host (the text is ONE scan's input, its records
+ * numbered in text order); records_limit: M (<= 0: the default; otherwise clamped as KVQ_OVER_RECORDS is).  WRITES
+ * out[0, kvq_over_len()). */
+int32_t        kvq_over_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t records_limit,
+                             int64_t *out);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -341,6 +384,7 @@ double  kvq_scan_main_kernel_ms(const kvq_scan *s);
 double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_profile_records alone (0 when the profile is off) */
 double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_profile_cycles alone (0 when the cycles are off) */
 double  kvq_scan_reads_kernel_ms(const kvq_scan *s);     /* ... and for kvq_reads_records and the table's settle kernels (0 when both are off) */
+double  kvq_scan_over_kernel_ms(const kvq_scan *s);      /* ... and for kvq_over_records alone (0 when the overrepresented sequences are off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 /* (measurement) how kvq_scan_finish put the hits of the finished scan in order:
@@ -490,6 +534,9 @@ kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
  * after it); without KVQ_FIND_PROFILE they are KVQ_ERR_RUNTIME. */
 #define KVQ_FIND_READ_STATS 128u
 #define KVQ_FIND_DUPLICATION 256u
+/* KVQ_FIND_OVERREPRESENTED: kvq_scan_set_overrepresented for the call (kvq_scan_over after it); without KVQ_FIND_PROFILE it is
+ * KVQ_ERR_RUNTIME. */
+#define KVQ_FIND_OVERREPRESENTED 512u
 typedef struct kvq_find_opts {
     uint32_t size, flags;
     int32_t  n_cutoffs;

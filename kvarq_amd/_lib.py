@@ -17,7 +17,8 @@ FIND_RECORDS = 4                                                 # kvq_findseqs_
 FIND_PROFILE = 8                                                 # kvq_findseqs_opts: profile the input
 FIND_CYCLES = 16                                                 # ... and count its bytes per cycle (with FIND_PROFILE)
 FIND_READ_STATS, FIND_DUPLICATION = 128, 256                     # ... the per-read distributions, the duplication (with FIND_PROFILE)
-READ_STATS, READ_DUPLICATION = 1, 2                              # kvq_scan_set_read_stats
+FIND_OVERREPRESENTED = 512                                       # ... the overrepresented sequences (with FIND_PROFILE)
+READ_STATS, READ_DUPLICATION = 1, 2                            # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
 # kvq_scan_path: a batch took the seed-filter kernel / the exhaustive kernels; a whole batch / the records of skipped tiles were redone;
@@ -132,6 +133,11 @@ PROTOTYPES = {
     'kvq_reads_host': (i32, [vp, i64, P(i64), i64, i64, P(i64), P(i64)]),
     'kvq_dup_hash_host': (u64, [vp, i64]),
     'kvq_scan_reads_kernel_ms': (C.c_double, [vp]),
+    'kvq_over_len': (i64, []),
+    'kvq_scan_set_overrepresented': (i32, [vp, i32]),
+    'kvq_scan_over': (P(i64), [vp]),
+    'kvq_over_host': (i32, [vp, i64, P(i64), i64, i64, P(i64)]),
+    'kvq_scan_over_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

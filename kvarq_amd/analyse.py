@@ -71,7 +71,8 @@ class Analyser(object):
         :meth:`extract_hits`.  ``profile=<cutoffs>`` keeps the ``kvarq_amd.profile.Profile`` of the input in
         ``self.profile`` (``encode`` then adds ``info['profile']``); ``cycles=True`` takes the per-cycle counts into it
         (``info['profile']['cycles']``), ``per_read=True`` / ``duplication=True`` the per-read distributions / the
-        duplication (``info['profile']['per_read']`` / ``['duplication']``); ``long_reads``: as for ``engine.findseqs``,
+        duplication (``info['profile']['per_read']`` / ``['duplication']``), ``overrepresented=True`` the overrepresented
+        sequences (``info['profile']['overrepresented']``); ``long_reads``: as for ``engine.findseqs``,
         which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()

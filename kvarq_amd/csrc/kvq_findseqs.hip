@@ -185,6 +185,10 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_READ_STATS and KVQ_FIND_DUPLICATION need KVQ_FIND_PROFILE (the per-read statistics ride on the profile)");
         return nullptr;
     }
+    if ((flags & KVQ_FIND_OVERREPRESENTED) && !(flags & KVQ_FIND_PROFILE)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_OVERREPRESENTED needs KVQ_FIND_PROFILE (the overrepresented sequences ride on the profile)");
+        return nullptr;
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -221,7 +225,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
               kvq_scan_set_long_reads(s, (flags & KVQ_FIND_LONG_READS) ? 1 : (flags & KVQ_FIND_LONG_READS_AUTO) ? 2 : 0) ||
               kvq_scan_set_profile(s, opts ? opts->cutoffs : nullptr, (flags & KVQ_FIND_PROFILE) ? opts->n_cutoffs : -1) ||
               kvq_scan_set_cycles(s, (flags & KVQ_FIND_CYCLES) ? 1 : 0) ||
-              kvq_scan_set_read_stats(s, ((flags & KVQ_FIND_READ_STATS) ? KVQ_READ_STATS : 0) | ((flags & KVQ_FIND_DUPLICATION) ? KVQ_READ_DUPLICATION : 0)))) {
+              kvq_scan_set_read_stats(s, ((flags & KVQ_FIND_READ_STATS) ? KVQ_READ_STATS : 0) | ((flags & KVQ_FIND_DUPLICATION) ? KVQ_READ_DUPLICATION : 0)) ||
+              kvq_scan_set_overrepresented(s, (flags & KVQ_FIND_OVERREPRESENTED) ? 1 : 0))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
     }
     const double tf1 = now_ms();
@@ -300,7 +305,7 @@ extern "C" kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
     kvq_find_opts o; memset(&o, 0, sizeof(o));
     o.size = (uint32_t)sizeof(o); o.flags = flags & ~(KVQ_FIND_PROFILE | KVQ_FIND_CYCLES);       // (the profile has cutoffs: kvq_findseqs_opts)
     // (... but for the per-read statistics, which need none: with them KVQ_FIND_PROFILE is a profile with no cutoffs)
-    if ((flags & (KVQ_FIND_READ_STATS | KVQ_FIND_DUPLICATION)) && (flags & KVQ_FIND_PROFILE)) o.flags = flags;
+    if ((flags & (KVQ_FIND_READ_STATS | KVQ_FIND_DUPLICATION | KVQ_FIND_OVERREPRESENTED)) && (flags & KVQ_FIND_PROFILE)) o.flags = flags;
     return kvq_findseqs_opts(files, nfiles, seqs, seqlens, nseq, &o);
 }
 

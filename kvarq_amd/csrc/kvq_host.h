@@ -142,7 +142,7 @@ int kvq_comm_max_status(kvq_comm *c, unsigned long long mine, unsigned long long
 
 // An input pass: a kernel that every batch runs once over its exact record index and that adds to one device array, which the
 // tail of the scan brings to the host.  The cycles' array has the kernel's own scratch word behind the words that land.
-enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASSES };
+enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASSES };
 typedef std::pair<hipEvent_t, hipEvent_t> KvqEventPair;
 struct KvqPass {
     bool on = false;
@@ -232,7 +232,8 @@ struct kvq_scan {
     int64_t rec_store_bytes = 0;                  // store bytes of the finished scan
     // the passes over a batch's exact record index (kvq_profile.hip; DESIGN section 13, "the lifecycle of an input pass"), in the
     // order they run: the profile of the input (kvq_scan_set_profile), the per-cycle counts beside it (kvq_scan_set_cycles) and what
-    // the individual reads look like (kvq_scan_set_read_stats).  The last two keep their buffers only while they are on
+    // the individual reads look like (kvq_scan_set_read_stats) and the overrepresented sequences (kvq_scan_set_overrepresented).  All but
+    // the first keep their buffers only while they are on
     KvqPass passes[KVQ_PASSES];
     int32_t prof_ncut = 0; uint8_t prof_cuts[KVQ_PROFILE_MAX_CUTOFFS] = { 0 };      // the profile's cutoffs
     // the reads pass: bit 0 of its mode the per-read distributions (the pass's array), bit 1 the duplication (d_dup: the state block,
@@ -240,6 +241,9 @@ struct kvq_scan {
     int32_t reads_mode = 0;
     DevBuf d_dup; uint64_t dup_slots = 0;
     std::vector<int64_t> h_dup;
+    // the overrepresented sequences: M, the slots of the table (the pass's array: KvqOverLayout), and the records the pass has seen
+    // since it was last cleared -- the first M of them make the candidates
+    uint64_t over_M = 0, over_slots = 0, over_seen = 0;
 };
 
 // kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal

@@ -1,7 +1,8 @@
-// kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14 and 16), host side: the profile, the
-// per-cycle counts and the per-read statistics as options of a scan object, the steps of their common lifecycle, the launch of
+// kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16 and 17), host side: the profile, the
+// per-cycle counts, the per-read statistics and the overrepresented sequences as options of a scan object, the steps of their common lifecycle, the launch of
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
+#include <array>
 #include <string.h>
 
 // ---- the lifecycle of an input pass: what the three share, written once ----
@@ -55,6 +56,26 @@ static KvqDupTable dup_table(const kvq_scan *s)
     return T;
 }
 
+// where the pieces lie inside the array of KVQ_PASS_OVER: the result array of kvq_over_select (the words that land), the state block, the table
+struct KvqOverLayout {
+    static constexpr size_t RESULT = 0, STATE = (size_t)KVQ_OVER_WORDS * 8, TABLE = STATE + 256;
+    static_assert(KvqOverState::WORDS * 8 <= 256 && STATE % 8 == 0, "the pieces of the array overlap");
+    static size_t bytes(uint64_t slots) { return TABLE + (size_t)slots * KVQ_OVER_ROW_WORDS * 8; }
+};
+static KvqOverTable over_table(const kvq_scan *s)
+{
+    KvqOverTable T; T.lg = 0;
+    char *p = (char *)s->passes[KVQ_PASS_OVER].d.p;
+    T.state = (unsigned long long *)(p + KvqOverLayout::STATE); T.slots = (unsigned long long *)(p + KvqOverLayout::TABLE);
+    while ((1ull << T.lg) < s->over_slots) T.lg++;
+    return T;
+}
+static void over_off(kvq_scan *s)
+{
+    s->over_M = s->over_slots = s->over_seen = 0;
+    pass_off(s, s->passes[KVQ_PASS_OVER]);
+}
+
 // the device arrays of the passes that are on (and the duplication's table: a zero state block is level 0 with table 0 active) back to
 // zero: wherever the hit arena is cleared (reset_device_state), so that a replay, a rescan round and a file read again count every record once
 static int pass_clear(kvq_scan *s, int which)
@@ -62,6 +83,7 @@ static int pass_clear(kvq_scan *s, int which)
     const KvqPass &p = s->passes[which];
     if (p.d_bytes) KVQ_HIP(hipMemsetAsync(p.d.p, 0, p.d_bytes, s->stream));
     if (which == KVQ_PASS_READS && (s->reads_mode & KVQ_READ_DUPLICATION)) KVQ_HIP(hipMemsetAsync(s->d_dup.p, 0, KvqDupLayout::bytes(s->dup_slots), s->stream));
+    if (which == KVQ_PASS_OVER) s->over_seen = 0;            // (the table is the pass's array: empty again, and the next record is number 0)
     return KVQ_OK;
 }
 static int passes_clear(kvq_scan *s)
@@ -74,6 +96,14 @@ static int passes_clear(kvq_scan *s)
 // active table behind the distributions; passes_landed: the finished scan's copies
 static int passes_tail(kvq_scan *s)
 {
+    if (s->passes[KVQ_PASS_OVER].on) {
+        // (in front of the copies: the result array is the part of the pass's array that lands)
+        unsigned long long *res = (unsigned long long *)((char *)s->passes[KVQ_PASS_OVER].d.p + KvqOverLayout::RESULT);
+        KVQ_HIP(hipMemsetAsync(res, 0, (size_t)KVQ_OVER_WORDS * 8, s->stream));
+        hipLaunchKernelGGL(kvq_over_select, dim3((uint32_t)std::min<uint64_t>(s->over_slots / 256, KVQ_OVER_GRID_MAX)), dim3(256), 0, s->stream,
+                           over_table(s), (unsigned long long)s->over_M, res);
+        KVQ_HIP(hipGetLastError());
+    }
     for (KvqPass &p : s->passes) if (p.on && p.words) KVQ_HIP(hipMemcpyAsync(p.pin, p.d.p, p.words * 8, hipMemcpyDeviceToHost, s->stream));
     if (s->reads_mode & KVQ_READ_DUPLICATION) {
         unsigned long long *res = (unsigned long long *)((char *)s->d_dup.p + KvqDupLayout::RESULT);
@@ -90,6 +120,19 @@ static void passes_landed(kvq_scan *s)
     if (s->reads_mode & KVQ_READ_DUPLICATION) {
         const int64_t *dup = s->passes[KVQ_PASS_READS].pin + KVQ_READS_WORDS;
         s->h_dup.assign(dup, dup + KVQ_DUP_WORDS);
+    }
+    if (s->passes[KVQ_PASS_OVER].on) {
+        // the rows landed in the order the slots' workgroups came by: into the canonical one -- count descending, ties by hash ascending as unsigned
+        typedef std::array<int64_t, KVQ_OVER_ROW_WORDS> Row;
+        std::vector<int64_t> &h = s->passes[KVQ_PASS_OVER].h;
+        h[KVQ_OVER_LISTED] = std::min<int64_t>(h[KVQ_OVER_LISTED], KVQ_OVER_MAX_ROWS);
+        std::vector<Row> rows((size_t)h[KVQ_OVER_LISTED]);
+        if (!rows.empty()) memcpy(rows.data(), h.data() + KVQ_OVER_ROWS, rows.size() * sizeof(Row));
+        std::sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) {
+            return a[KVQ_OVER_ROW_COUNT] != b[KVQ_OVER_ROW_COUNT] ? a[KVQ_OVER_ROW_COUNT] > b[KVQ_OVER_ROW_COUNT]
+                                                                  : (uint64_t)a[KVQ_OVER_ROW_HASH] < (uint64_t)b[KVQ_OVER_ROW_HASH];
+        });
+        if (!rows.empty()) memcpy(h.data() + KVQ_OVER_ROWS, rows.data(), rows.size() * sizeof(Row));
     }
 }
 // what an accessor hands out: the copy of a pass that is on, of a finished scan
@@ -110,7 +153,7 @@ extern "C" int32_t kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int
     int rc;
     kvq_clear_error();
     if ((rc = scan_idle(s, "kvq_scan_set_profile"))) return rc;
-    if (ncut < 0) { s->passes[KVQ_PASS_PROFILE].on = false; s->prof_ncut = 0; pass_off(s, s->passes[KVQ_PASS_CYCLES]); reads_off(s); return KVQ_OK; }
+    if (ncut < 0) { s->passes[KVQ_PASS_PROFILE].on = false; s->prof_ncut = 0; pass_off(s, s->passes[KVQ_PASS_CYCLES]); reads_off(s); over_off(s); return KVQ_OK; }
     if (ncut > KVQ_PROFILE_MAX_CUTOFFS || (ncut > 0 && !cutoffs)) {
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_profile: at most %d cutoffs", KVQ_PROFILE_MAX_CUTOFFS);
         return KVQ_ERR_RUNTIME;
@@ -261,3 +304,46 @@ static int reads_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
 
 extern "C" const int64_t *kvq_scan_reads(const kvq_scan *s) { return pass_result(s, KVQ_PASS_READS); }
 extern "C" const int64_t *kvq_scan_dup(const kvq_scan *s) { return (s->reads_mode & KVQ_READ_DUPLICATION) && s->finished && !s->h_dup.empty() ? s->h_dup.data() : nullptr; }
+
+// ---- overrepresented sequences ----
+extern "C" int64_t kvq_over_len(void) { return KVQ_OVER_WORDS; }
+
+extern "C" int32_t kvq_scan_set_overrepresented(kvq_scan *s, int32_t on)
+{
+    int rc;
+    kvq_clear_error();
+    if ((rc = scan_idle(s, "kvq_scan_set_overrepresented"))) return rc;
+    if (!on) { over_off(s); return KVQ_OK; }
+    if (!s->passes[KVQ_PASS_PROFILE].on) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_overrepresented: the scan keeps no profile (the overrepresented sequences ride on its record set and index: kvq_scan_set_profile first)");
+        return KVQ_ERR_RUNTIME;
+    }
+    const char *e = getenv("KVQ_OVER_RECORDS");
+    const uint64_t M = over_records_from(e ? atoll(e) : 0), slots = over_slots_from(M);
+    if (slots != s->over_slots) over_off(s);                 // (a kept scan object asked for the same again keeps its buffers)
+    if ((rc = pass_make(s->passes[KVQ_PASS_OVER], KvqOverLayout::bytes(slots), KVQ_OVER_WORDS, (size_t)KVQ_OVER_WORDS * 8))) { over_off(s); return rc; }
+    s->over_M = M; s->over_slots = slots;
+    return pass_clear(s, KVQ_PASS_OVER);
+}
+
+// the pass over the R records of a batch, behind its other passes: the records with a number below M make candidates (INSERT), the
+// rest are looked up -- two launches for the one batch that M cuts, in that order on the scan's stream; one for every other
+static int over_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    const uint64_t n_insert = std::min(R, s->over_seen < s->over_M ? s->over_M - s->over_seen : 0);
+    const KvqOverTable T = over_table(s);
+    const uint64_t cut[3] = { 0, n_insert, R };
+    for (int mode = 0; mode < 2; mode++) {
+        const uint64_t r0 = cut[mode], r1 = cut[mode + 1];
+        if (r0 == r1) continue;
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((r1 - r0 + 63) / 64, 2048);             // (the kernel strides over what there is)
+        hipLaunchKernelGGL(kvq_over_records, dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)r0, (uint32_t)r1,
+                           mode == 0 ? 1u : 0u, T);
+    }
+    KVQ_HIP(hipGetLastError());
+    s->over_seen += R;
+    return KVQ_OK;
+}
+
+extern "C" const int64_t *kvq_scan_over(const kvq_scan *s) { return pass_result(s, KVQ_PASS_OVER); }

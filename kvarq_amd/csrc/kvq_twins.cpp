@@ -1,11 +1,13 @@
-// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes (include/kvarq_hip.h, DESIGN sections 13, 14 and 16): the
-// definitions of kvq_profile_records, kvq_profile_cycles and kvq_reads_records in plain C++ (test infrastructure, never a
-// fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record walk serve all three.
+// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16 and 17): the
+// definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records and kvq_over_records in plain C++ (test infrastructure,
+// never a fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record walk serve all four.
 #include "../../include/kvarq_hip.h"
 #include "kvq_dup_hash.h"
 #include <algorithm>
 #include <string.h>
 #include <unordered_map>
+#include <utility>
+#include <vector>
 
 void kvq_set_error(int code, const char *fmt, ...);      // (kvq_runtime.hip)
 void kvq_clear_error();
@@ -18,6 +20,20 @@ static uint64_t dup_slots_from(long long wish)
     uint64_t c = KVQ_DUP_MIN_SLOTS;
     while (2 * c <= (uint64_t)wish) c *= 2;
     return c;
+}
+
+// M of the overrepresented sequences from a wish: the default, or the wish clamped (kvq_scan_set_overrepresented reads it from
+// KVQ_OVER_RECORDS); the slots of a table for M candidates: four times M rounded up to a power of two, at least 1024
+static uint64_t over_records_from(long long wish)
+{
+    if (wish <= 0) return KVQ_OVER_DEFAULT_RECORDS;
+    return (uint64_t)std::min<long long>(std::max<long long>(wish, KVQ_OVER_MIN_RECORDS), KVQ_OVER_MAX_RECORDS);
+}
+static uint64_t over_slots_from(uint64_t M)
+{
+    uint64_t c = 256;
+    while (c < M) c *= 2;
+    return 4 * c;
 }
 
 // what every twin asks of its text and chunk table (`ok`: what it asks beyond that)
@@ -88,6 +104,55 @@ extern "C" int32_t kvq_reads_host(const uint8_t *text, int64_t nbytes, const int
         const uint32_t b = kvq_dup_bin((uint64_t)k.second);
         dup_out[KVQ_DUP_DISTINCT + b]++; dup_out[KVQ_DUP_RECORDS + b] += k.second;
         dup_out[KVQ_DUP_TRACKED_KEYS]++; dup_out[KVQ_DUP_TRACKED_RECORDS] += k.second;
+    }
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_over_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t records_limit,
+                                 int64_t *out)
+{
+    if (!twin_args("kvq_over_host", out != nullptr, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    struct Cand { int64_t count = 0, n = 0; uint8_t key[KVQ_DUP_KEY_BYTES] = { 0 }; };
+    const uint64_t M = over_records_from(records_limit);
+    std::unordered_map<uint64_t, Cand> cands;                                  // the keys of the first M records, by their hash
+    int64_t keyed = 0, unkeyed = 0;
+    uint64_t number = 0;
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t, int64_t) {
+        const uint8_t *bases = text + n0 + 1;
+        int64_t L = n1 - n0 - 1;
+        if (L > 0 && bases[L - 1] == '\r') L--;                                // a trailing '\r' is not part of its line
+        const uint64_t mine = number++;
+        if (L == 0) { unkeyed++; return; }
+        keyed++;
+        const uint64_t h = kvq_dup_hash(bases, (uint64_t)L);
+        auto at = cands.find(h);
+        if (at == cands.end()) {
+            if (mine >= M) return;                                              // no candidate: counted nowhere but in `keyed`
+            at = cands.emplace(h, Cand()).first;                                // (the bytes of whichever key came first to the hash)
+            at->second.n = std::min<int64_t>(L, KVQ_DUP_KEY_BYTES);
+            memcpy(at->second.key, bases, (size_t)at->second.n);
+        }
+        at->second.count++;
+    });
+    memset(out, 0, (size_t)KVQ_OVER_WORDS * 8);
+    out[KVQ_OVER_M] = (int64_t)M; out[KVQ_OVER_SLOTS] = (int64_t)over_slots_from(M); out[KVQ_OVER_KEYED] = keyed; out[KVQ_OVER_UNKEYED] = unkeyed;
+    std::vector<std::pair<uint64_t, const Cand *>> listed;
+    for (const auto &c : cands) {
+        out[KVQ_OVER_CANDIDATES]++; out[KVQ_OVER_COUNTED] += c.second.count;
+        if (c.second.count >= 2 && 1000 * c.second.count >= keyed) listed.emplace_back(c.first, &c.second);
+    }
+    std::sort(listed.begin(), listed.end(), [](const std::pair<uint64_t, const Cand *> &a, const std::pair<uint64_t, const Cand *> &b) {
+        return a.second->count != b.second->count ? a.second->count > b.second->count : a.first < b.first;
+    });
+    out[KVQ_OVER_LISTED] = (int64_t)listed.size();                              // (at most KVQ_OVER_MAX_ROWS: the counts sum to at most `keyed`)
+    for (size_t r = 0; r < listed.size(); r++) {
+        int64_t *row = out + KVQ_OVER_ROWS + (int64_t)r * KVQ_OVER_ROW_WORDS;
+        row[KVQ_OVER_ROW_HASH] = (int64_t)listed[r].first; row[KVQ_OVER_ROW_COUNT] = listed[r].second->count; row[KVQ_OVER_ROW_N] = listed[r].second->n;
+        for (int i = 0; i < 8; i++) {
+            uint64_t w = 0;
+            for (int j = 0; j < 8; j++) w |= (uint64_t)listed[r].second->key[8 * i + j] << (8 * j);
+            row[KVQ_OVER_ROW_KEY + i] = (int64_t)w;
+        }
     }
     return KVQ_OK;
 }

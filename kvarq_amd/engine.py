@@ -203,6 +203,11 @@ def findseqs(fname, sequences, *, inflate='host', **options):
     bases repeat (``Profile.duplication``).  Without ``profile`` either means a
     profile with no cutoffs.
 
+    overrepresented=True: that profile also lists the sequences (the reads' first 64 bases) that make
+    up 0.1 % of the reads and more, among those seen in the first 2^18 records, each counted through
+    the whole input (``Profile.overrepresented``).  Without ``profile`` it means a
+    profile with no cutoffs.
+
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
     no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are

@@ -1,6 +1,6 @@
 """
 The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
-``duplication`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+``duplication``, ``overrepresented`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
 everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
 """
 import ctypes as C
@@ -12,14 +12,16 @@ class ScanOptions(object):
     """``records``: keep the FastQ record of every hit; ``profile``: the cutoffs of the input's profile
     (``profile.as_cutoffs``; True: ``amin``, or the configured Amin; None: no profile) -- a list of byte values here;
     ``cycles``: the per-cycle counts beside it; ``read_stats``: the mode bits of kvq_scan_set_read_stats for ``per_read`` and
-    ``duplication``; ``long_mode``: the mode of kvq_scan_set_long_reads for ``long_reads`` (False, True or 'auto').
-    ``cycles``, ``per_read`` or ``duplication`` without ``profile`` mean a profile with no cutoffs."""
+    ``duplication``; ``overrepresented``: the overrepresented sequences; ``long_mode``: the mode of kvq_scan_set_long_reads
+    for ``long_reads`` (False, True or 'auto').
+    ``cycles``, ``per_read``, ``duplication`` or ``overrepresented`` without ``profile`` mean a profile with no cutoffs."""
 
-    def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, amin=None):
+    def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, overrepresented=False,
+                 amin=None):
         self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
-        self.records, self.cycles = bool(records), bool(cycles)
+        self.records, self.cycles, self.overrepresented = bool(records), bool(cycles), bool(overrepresented)
         self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
-        if (self.cycles or self.read_stats) and profile is None:
+        if (self.cycles or self.read_stats or self.overrepresented) and profile is None:
             profile = ()
         self.profile = None
         if profile is not None:
@@ -31,7 +33,7 @@ class ScanOptions(object):
         flags |= (0, _lib.FIND_LONG_READS, _lib.FIND_LONG_READS_AUTO)[self.long_mode] | (_lib.FIND_RECORDS if self.records else 0)
         if self.profile is not None:
             flags |= (_lib.FIND_PROFILE | (_lib.FIND_CYCLES if self.cycles else 0) | (_lib.FIND_READ_STATS if self.read_stats & _lib.READ_STATS else 0) |
-                      (_lib.FIND_DUPLICATION if self.read_stats & _lib.READ_DUPLICATION else 0))
+                      (_lib.FIND_DUPLICATION if self.read_stats & _lib.READ_DUPLICATION else 0) | (_lib.FIND_OVERREPRESENTED if self.overrepresented else 0))
         cuts = self.profile or ()
         return _lib.FindOpts(C.sizeof(_lib.FindOpts), flags, len(cuts), (C.c_uint8 * 8)(*cuts))
 
@@ -44,6 +46,8 @@ class ScanOptions(object):
                 calls.append(('kvq_scan_set_cycles', (1,)))
             if self.read_stats:
                 calls.append(('kvq_scan_set_read_stats', (self.read_stats,)))
+            if self.overrepresented:
+                calls.append(('kvq_scan_set_overrepresented', (1,)))
         if self.long_mode:
             calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
         return calls

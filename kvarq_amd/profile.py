@@ -17,8 +17,15 @@ per-read GC share, mean quality and N count (``Profile.gc_hist`` and what follow
 GC peak that no sum over reads can show --, with ``duplication=True`` how often the reads' first 64 bases repeat
 (``Profile.duplication``, ``Profile.duplicate_share()``); ``--per-read`` and ``--duplication`` print them.
 
+With ``overrepresented=True`` it tells WHICH SEQUENCES the duplicates are: ``Profile.overrepresented``
+lists every sequence (a read's first 64 bases) that makes up 0.1 % of the reads and more, with its exact count in the whole
+input and a label of where it may come from (``KNOWN_SOURCES``); ``--overrepresented`` prints the list.  The candidates are
+the sequences among the first 2^18 records: a sequence that first shows up behind them is not found, which in a file that is
+not sorted has a probability of e^-262 at a share of 0.1 %.
+
 Out of scope: profiles across ranks, and what ``Fastq`` guesses by default.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -41,6 +48,50 @@ READS_RECORDS, READS_GC_NONE, READS_MEANQ_NONE, READS_GC, READS_GC_BINS, READS_M
 DUP_HEADER = ('level', 'slots', 'keyed', 'unkeyed', 'tracked_records', 'tracked_distinct')
 DUP_DISTINCT, DUP_RECORDS, DUP_BINS, DUP_LEN = 8, 24, 16, 40
 DUP_BOUNDS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)        # the lower bounds of the count bins
+
+
+# the overrepresented sequences (include/kvarq_hip.h: kvq_over_len()): the header words, then rows {hash, count, n, w0 .. w7}
+OVER_HEADER = ('records_limit', 'slots', 'keyed', 'unkeyed', 'candidates', 'counted', 'listed')
+OVER_ROWS, OVER_ROW_WORDS, OVER_MAX_ROWS = 8, 11, 1000
+OVER_LEN = OVER_ROWS + OVER_MAX_ROWS * OVER_ROW_WORDS
+
+Overrepresented = collections.namedtuple('Overrepresented', 'sequence count share hash source')
+
+
+def _poly(base):
+    def probe(sequence):
+        return 10 * sequence.count(base) >= 9 * len(sequence)
+    return probe
+
+
+# Where an overrepresented sequence may come from: label -> probe, in the order they are tried; the first that matches is the
+# row's ``source``.  A probe of bytes matches when it or its reverse complement occurs in the sequence, a callable when it
+# returns true for the sequence.  The adapter probes (the first twelve bases of each) were written down from memory of FastQC's
+# public adapter list, not copied from it: check them against your kit before you rely on a label.  poly-X: one byte makes up
+# 90 % of the sequence or more (poly-G: the tail of a two-colour instrument that reads no signal).  Replace or extend the
+# mapping, or pass one as ``sources=``.
+KNOWN_SOURCES = collections.OrderedDict([
+    ('Illumina universal adapter', b'AGATCGGAAGAG'),
+    ("Illumina small RNA 3' adapter", b'TGGAATTCTCGG'),
+    ("Illumina small RNA 5' adapter", b'GATCGTCGGACT'),
+    ('Nextera transposase', b'CTGTCTCTTATA'),
+    ('poly-A', _poly(b'A')), ('poly-C', _poly(b'C')), ('poly-G', _poly(b'G')), ('poly-T', _poly(b'T')), ('poly-N', _poly(b'N')),
+])
+
+_COMPLEMENT = bytes.maketrans(b'ACGTacgt', b'TGCAtgca')
+
+
+def source_of(sequence, sources=None):
+    """the label of the first entry of ``sources`` (None: ``KNOWN_SOURCES``) that matches ``sequence``, or None"""
+    for label, probe in (KNOWN_SOURCES if sources is None else sources).items():
+        if callable(probe):
+            if probe(sequence):
+                return label
+        else:
+            probe = probe.encode('latin-1') if isinstance(probe, str) else bytes(probe)
+            if probe and (probe in sequence or probe.translate(_COMPLEMENT)[::-1] in sequence):
+                return label
+    return None
 
 
 def profile_len(ncut):
@@ -130,10 +181,20 @@ class Profile(object):
     ``mean_quality_hist`` (256 bins: the reads by their mean score BYTE), ``n_hist`` (256 bins: the reads by their N
     count, 255 and more in the last);
     ``duplication``: a dict of the header words of kvq_scan_dup (``DUP_HEADER``) and its two rows of 16 bins,
-    'distinct' and 'records' (``DUP_BOUNDS``: their lower bounds), or None"""
+    'distinct' and 'records' (``DUP_BOUNDS``: their lower bounds), or None;
+    ``over``: the flat array of kvq_scan_over (kvq_over_len() words) when the scan took it, else None -- ``over_info``: its
+    header words by name (``OVER_HEADER``), ``overrepresented``: its rows in their canonical order (count descending, ties by
+    hash ascending) as named tuples ``(sequence: bytes, count, share = count / keyed, hash, source)``, ``source`` the label
+    of ``source_of`` under ``sources`` (None: ``KNOWN_SOURCES``)"""
 
-    def __init__(self, words, cutoffs, cycles=None, reads=None, dup=None):
+    def __init__(self, words, cutoffs, cycles=None, reads=None, dup=None, over=None, sources=None):
         self.cutoffs = list(cutoffs)
+        self.over = self.over_info = self.overrepresented = None
+        if over is not None:
+            self.over = np.array(over, dtype=np.int64)
+            assert self.over.shape == (OVER_LEN,)
+            self.over_info = dict(zip(OVER_HEADER, (int(v) for v in self.over[:len(OVER_HEADER)])))
+            self.relabel(sources)
         self.reads = self.duplication = None
         if reads is not None:
             self.reads = np.array(reads, dtype=np.int64)
@@ -160,8 +221,10 @@ class Profile(object):
     def __eq__(self, other):
         if not (isinstance(other, Profile) and self.cutoffs == other.cutoffs and (self.words == other.words).all()):
             return False
-        if self.duplication != other.duplication:
+        if self.duplication != other.duplication or self.over_info != other.over_info:
             return False
+        if self.over is not None and [r[:4] for r in self.overrepresented] != [r[:4] for r in other.overrepresented]:
+            return False                                  # (the labels are the host's reading of the rows, not a part of them)
         for a, b in ((self.reads, other.reads), (self.cycles, other.cycles)):
             if (a is None) != (b is None) or (a is not None and not (a == b).all()):
                 return False
@@ -375,6 +438,33 @@ class Profile(object):
             lines.append('copies %s: distinct=%d reads=%d' % (span, d['distinct'][i], d['records'][i]))
         return lines
 
+    # -- overrepresented sequences -----------------------------------------------
+
+    def relabel(self, sources=None):
+        """read the rows again, their ``source`` from ``sources`` (None: ``KNOWN_SOURCES``); returns the list"""
+        if self.over is None:
+            raise ValueError('this profile was taken without overrepresented=True')
+        keyed = self.over_info['keyed']
+        rows = self.over[OVER_ROWS:OVER_ROWS + OVER_ROW_WORDS * self.over_info['listed']].reshape(-1, OVER_ROW_WORDS)
+        self.overrepresented = []
+        for row in rows:
+            sequence = row[3:].astype('<i8').tobytes()[:int(row[2])]
+            self.overrepresented.append(Overrepresented(sequence, int(row[1]), int(row[1]) / float(keyed), int(row[0]) & 0xFFFFFFFFFFFFFFFF,
+                                                        source_of(sequence, sources)))
+        return self.overrepresented
+
+    def overrepresented_lines(self):
+        """the overrepresented part of the command line: what was looked at, then a line per listed sequence"""
+        if self.over is None:
+            raise ValueError('this profile was taken without overrepresented=True')
+        o = self.over_info
+        lines = ['overrepresented: %d sequences of 0.1 %% and more among the %d candidates of the first %d records (keyed=%d unkeyed=%d counted=%d)'
+                 % (o['listed'], o['candidates'], o['records_limit'], o['keyed'], o['unkeyed'], o['counted'])]
+        for r in self.overrepresented:
+            lines.append('%s %d %.4f%% %s' % (r.sequence.decode('latin-1').encode('unicode_escape').decode('ascii'), r.count, 100 * r.share,
+                                             r.source or 'no known source'))
+        return lines
+
     def summary(self):
         lines = ['records=%d mismatched=%d longest=%d' % (self.records, self.mismatched, self.longest)]
         lo_, hi = self.score_range()
@@ -408,26 +498,31 @@ class Profile(object):
                              'gc': bins(self.gc_hist), 'mean_quality_byte': bins(self.mean_quality_hist), 'n': bins(self.n_hist)}
         if self.duplication is not None:
             d['duplication'] = dict(self.duplication, bounds=list(DUP_BOUNDS))
+        if self.over is not None:
+            d['overrepresented'] = dict(self.over_info, rows=[dict(r._asdict(), sequence=r.sequence.decode('latin-1')) for r in self.overrepresented])
         return d
 
 
-def from_scan(L, h):
-    """the profile of a finished scan object (kvq_scan_profile), None when it keeps none"""
+def from_scan(L, h, sources=None):
+    """the profile of a finished scan object (kvq_scan_profile), None when it keeps none; ``sources``: as for ``Profile``"""
     cuts = (C.c_uint8 * MAX_CUTOFFS)()
     n = L.kvq_scan_profile_cutoffs(h, cuts)
     ptr = L.kvq_scan_profile(h)
     if n < 0 or not ptr:
         return None
-    cyc, reads, dup = L.kvq_scan_cycles(h), L.kvq_scan_reads(h), L.kvq_scan_dup(h)
+    cyc, reads, dup, over = L.kvq_scan_cycles(h), L.kvq_scan_reads(h), L.kvq_scan_dup(h), L.kvq_scan_over(h)
     return Profile(np.ctypeslib.as_array(ptr, shape=(profile_len(n),)).copy(), list(cuts)[:n],
                    np.ctypeslib.as_array(cyc, shape=(CYCLES_LEN,)).copy() if cyc else None,
                    np.ctypeslib.as_array(reads, shape=(READS_LEN,)).copy() if reads else None,
-                   np.ctypeslib.as_array(dup, shape=(DUP_LEN,)).copy() if dup else None)
+                   np.ctypeslib.as_array(dup, shape=(DUP_LEN,)).copy() if dup else None,
+                   np.ctypeslib.as_array(over, shape=(OVER_LEN,)).copy() if over else None, sources)
 
 
-def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False, duplication=False, slots=0):
+def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False, duplication=False, slots=0, overrepresented=False,
+                 over_records=0, sources=None):
     """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host; per_read / duplication: and kvq_reads_host, with a
-    table of ``slots`` slots, 0: the default) over a text in host memory; chunk_off None: the reader's chunk cuts"""
+    table of ``slots`` slots, 0: the default; overrepresented: and kvq_over_host, with the first ``over_records`` records
+    making the candidates, 0: the default) over a text in host memory; chunk_off None: the reader's chunk cuts"""
     from . import scan
     cuts = as_cutoffs(cutoffs)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
@@ -450,15 +545,25 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False,
                                      reads.ctypes.data_as(C.POINTER(C.c_int64)) if per_read else None,
                                      dup.ctypes.data_as(C.POINTER(C.c_int64)) if duplication else None):
             raise RuntimeError(_lib.last_error()[1])
-    return Profile(out, cuts, cyc, reads, dup)
+    over = None
+    if overrepresented:
+        over = np.zeros(OVER_LEN, dtype=np.int64)
+        if _lib.lib().kvq_over_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+                                    int(over_records), over.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError(_lib.last_error()[1])
+    return Profile(out, cuts, cyc, reads, dup, over, sources)
 
 
-def profile(fnames, cutoffs=True, inflate='host', **options):
+def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
-    per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication; ``long_reads``:
-    as for ``engine.findseqs``, which takes the ``options``"""
+    per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication; ``overrepresented``:
+    with the overrepresented sequences, labelled from ``sources`` (None: ``KNOWN_SOURCES``); ``long_reads``: as for
+    ``engine.findseqs``, which takes the ``options``"""
     from . import engine
-    return engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)['profile']
+    p = engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)['profile']
+    if sources is not None and p.over is not None:
+        p.relabel(sources)
+    return p
 
 
 def main(argv=None):
@@ -472,8 +577,9 @@ def main(argv=None):
     ap.add_argument('--cycle-step', type=int, default=1, metavar='N', help='a line per N cycles')
     ap.add_argument('--per-read', action='store_true', help='the per-read GC histogram in 5 %% steps with its mean, the quantiles of the per-read mean quality, the share of reads with any N')
     ap.add_argument('--duplication', action='store_true', help='how often the first 64 bases of the reads repeat: level, sample size and a line per count bin')
+    ap.add_argument('--overrepresented', action='store_true', help='the sequences (first 64 bases) that make up 0.1 %% of the reads and more, among those of the first 2^18 records: count, share, known source')
     a = ap.parse_args(argv)
-    more = dict(cycles=a.cycles, per_read=a.per_read, duplication=a.duplication)
+    more = dict(cycles=a.cycles, per_read=a.per_read, duplication=a.duplication, overrepresented=a.overrepresented)
     p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
@@ -485,6 +591,8 @@ def main(argv=None):
         print('\n'.join(p.per_read_lines()))
     if a.duplication:
         print('\n'.join(p.duplication_lines()))
+    if a.overrepresented:
+        print('\n'.join(p.overrepresented_lines()))
 
 
 if __name__ == '__main__':
