@@ -376,6 +376,48 @@ const int64_t *kvq_scan_over(const kvq_scan *s);
 int32_t        kvq_over_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t records_limit,
                              int64_t *out);
 
+/* ---- adapter content: WHERE ADAPTERS BEGIN, PER READ ----
+ * Record set, bases line, '\r': the record set and the bases line are the profile's; as for the duplication a trailing '\r' is not
+ * part of the line.  L is the line's length after that.
+ * PROBES: n probes, 1 <= n <= 8 (KVQ_ADAPT_MAX_PROBES), each m_k bytes long, 8 <= m_k <= 32 (KVQ_ADAPT_MIN_PROBE ..
+ * KVQ_ADAPT_MAX_PROBE), every byte one of upper-case A C G T; anything else is refused with KVQ_ERR_RUNTIME.  Matching is on BYTES:
+ * 'a' does not match 'A', 'N' matches nothing.  (A kernel that compares the 2-bit codes (byte >> 1) & 3 must also know that the
+ * bytes are upper-case A C G T: 'G' and 'N' share a code, and so do a base and its lower-case letter.)
+ * PER RECORD AND PROBE k: FIRST_k is the smallest p with p + m_k <= L and line[p, p + m_k) == probe_k, "none" when there is no such
+ * p.  TAIL_k is considered only when FIRST_k is none: the largest t with T <= t <= min(m_k - 1, L) and line[L - t, L) ==
+ * probe_k[0, t), otherwise "none".  T = 6 (KVQ_ADAPT_MIN_TAIL): a choice, not a measurement -- a random tail matches a probe with
+ * probability about 4/3 * 4^-6 = 0.03 %.
+ * CLIP of the record is the minimum of FIRST_k over all probes k that have one, of L - TAIL_k over all probes k that have a tail
+ * match, and of L: the length an adapter clip would leave.
+ * THE RESULT: one flat int64 array of kvq_adapt_len() = 8 + 8 * 1064 + 1025 = 9545 words.  Every word is a sum; the result is
+ * independent of batch cuts, launches, routes and rescans.
+ *   [0] n     [1] records     [2] records with a full occurrence of any probe
+ *   [3] records with no full occurrence of any probe but a tail match of one     [4..7] 0
+ *   [8 + 1064 k .. +1064): the block of probe k (blocks of k >= n are zero):
+ *       +0 m_k     +1 records with FIRST_k     +2 of those, the records with FIRST_k >= 1024     +3 records with TAIL_k     +4..7 0
+ *       +8 .. +1032: first_k[p] for p < 1024     +1032 .. +1064: tail_k[t] (words with t < T or t >= m_k stay 0)
+ *   [8520 .. +1025): clip[min(CLIP, 1024)]
+ *   sum(first_k) + block[2] == block[1], sum(tail_k) == block[3], sum(clip) == [1] == the profile's records, [2] + [3] <= [1];
+ *   clip == the profile's raw_lengths word for word on an input without any match and without '\r'.
+ * kvq_scan_set_adapters: n probes of lens[k] bytes turn the pass on, n == 0 turns it off; rules as for kvq_scan_set_cycles: before
+ * the first batch or after kvq_scan_reset, KVQ_ERR_RUNTIME when the scan keeps no profile (and therefore with a communicator), off
+ * together with the profile.  Every batch is then counted once, behind its other passes; wherever the profile is cleared the array
+ * is.  kvq_scan_adapters: the array (valid after kvq_scan_finish until the next reset), NULL when the option is off.  The device
+ * array and the landing buffer exist only while the option is on; off, nothing is enqueued or allocated. */
+enum { KVQ_ADAPT_N = 0, KVQ_ADAPT_RECORDS = 1, KVQ_ADAPT_WITH_FULL = 2, KVQ_ADAPT_TAIL_ONLY = 3, KVQ_ADAPT_BLOCKS = 8,
+       KVQ_ADAPT_BLOCK_WORDS = 1064, KVQ_ADAPT_B_M = 0, KVQ_ADAPT_B_FIRST = 1, KVQ_ADAPT_B_BEYOND = 2, KVQ_ADAPT_B_TAIL = 3,
+       KVQ_ADAPT_B_FIRST_BINS = 8, KVQ_ADAPT_POSITIONS = 1024, KVQ_ADAPT_B_TAIL_BINS = 1032, KVQ_ADAPT_MAX_PROBES = 8,
+       KVQ_ADAPT_MIN_PROBE = 8, KVQ_ADAPT_MAX_PROBE = 32, KVQ_ADAPT_MIN_TAIL = 6, KVQ_ADAPT_CLIP = 8 + 8 * 1064,
+       KVQ_ADAPT_CLIP_BINS = 1025, KVQ_ADAPT_WORDS = 8 + 8 * 1064 + 1025 };
+int64_t        kvq_adapt_len(void);
+int32_t        kvq_scan_set_adapters(kvq_scan *s, const uint8_t *const *probes, const int32_t *lens, int32_t n);
+const int64_t *kvq_scan_adapters(const kvq_scan *s);
+/* host only, plain C++: the CPU twin of kvq_adapt_records over the same definition -- test infrastructure and the definition in
+ * running code, not a fallback.  Arguments as for kvq_profile_host; probes as for kvq_scan_set_adapters (n == 0 is refused here).
+ * ADDS into out[0, kvq_adapt_len()), but for [0] and the blocks' +0, which it sets. */
+int32_t        kvq_adapt_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                              const uint8_t *const *probes, const int32_t *lens, int32_t n, int64_t *out);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -385,6 +427,7 @@ double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_prof
 double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_profile_cycles alone (0 when the cycles are off) */
 double  kvq_scan_reads_kernel_ms(const kvq_scan *s);     /* ... and for kvq_reads_records and the table's settle kernels (0 when both are off) */
 double  kvq_scan_over_kernel_ms(const kvq_scan *s);      /* ... and for kvq_over_records alone (0 when the overrepresented sequences are off) */
+double  kvq_scan_adapt_kernel_ms(const kvq_scan *s);     /* ... and for kvq_adapt_records alone (0 when the adapters are off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 /* (measurement) how kvq_scan_finish put the hits of the finished scan in order:
@@ -542,6 +585,16 @@ typedef struct kvq_find_opts {
     int32_t  n_cutoffs;
     uint8_t  cutoffs[8];
 } kvq_find_opts;
+/* KVQ_FIND_ADAPTERS: kvq_scan_set_adapters for the call (kvq_scan_adapters after it); without KVQ_FIND_PROFILE it is
+ * KVQ_ERR_RUNTIME.  kvq_find_opts keeps its 20 bytes: the probes ride in a longer structure that begins with it, which the
+ * library reads only when the flag is set and base.size covers it -- anything else is "bad size". */
+#define KVQ_FIND_ADAPTERS 1024u
+typedef struct kvq_find_opts_adapters {
+    kvq_find_opts base;                  /* base.size: sizeof(kvq_find_opts_adapters) */
+    int32_t  n_probes;
+    uint8_t  lens[8];
+    uint8_t  probes[8][32];
+} kvq_find_opts_adapters;
 kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
                             const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts);
 

@@ -18,6 +18,7 @@ FIND_PROFILE = 8                                                 # kvq_findseqs_
 FIND_CYCLES = 16                                                 # ... and count its bytes per cycle (with FIND_PROFILE)
 FIND_READ_STATS, FIND_DUPLICATION = 128, 256                     # ... the per-read distributions, the duplication (with FIND_PROFILE)
 FIND_OVERREPRESENTED = 512                                       # ... the overrepresented sequences (with FIND_PROFILE)
+FIND_ADAPTERS = 1024                                             # ... the adapter content (with FIND_PROFILE; the probes in FindOptsAdapters)
 READ_STATS, READ_DUPLICATION = 1, 2                            # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
@@ -47,6 +48,11 @@ class LiveStats(C.Structure):
 
 class FindOpts(C.Structure):
     _fields_ = [('size', C.c_uint32), ('flags', C.c_uint32), ('n_cutoffs', C.c_int32), ('cutoffs', C.c_uint8 * 8)]
+
+
+class FindOptsAdapters(C.Structure):
+    """kvq_find_opts_adapters: the 20 bytes of kvq_find_opts, then the probes of FIND_ADAPTERS"""
+    _fields_ = [('base', FindOpts), ('n_probes', C.c_int32), ('lens', C.c_uint8 * 8), ('probes', (C.c_uint8 * 32) * 8)]
 
 
 class GzipReport(C.Structure):
@@ -138,6 +144,11 @@ PROTOTYPES = {
     'kvq_scan_over': (P(i64), [vp]),
     'kvq_over_host': (i32, [vp, i64, P(i64), i64, i64, P(i64)]),
     'kvq_scan_over_kernel_ms': (C.c_double, [vp]),
+    'kvq_adapt_len': (i64, []),
+    'kvq_scan_set_adapters': (i32, [vp, P(cp), P(i32), i32]),
+    'kvq_scan_adapters': (P(i64), [vp]),
+    'kvq_adapt_host': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, P(i64)]),
+    'kvq_scan_adapt_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

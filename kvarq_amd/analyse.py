@@ -72,7 +72,7 @@ class Analyser(object):
         ``self.profile`` (``encode`` then adds ``info['profile']``); ``cycles=True`` takes the per-cycle counts into it
         (``info['profile']['cycles']``), ``per_read=True`` / ``duplication=True`` the per-read distributions / the
         duplication (``info['profile']['per_read']`` / ``['duplication']``), ``overrepresented=True`` the overrepresented
-        sequences (``info['profile']['overrepresented']``); ``long_reads``: as for ``engine.findseqs``,
+        sequences (``info['profile']['overrepresented']``), ``adapters=`` the adapter content (``info['profile']['adapters']``); ``long_reads``: as for ``engine.findseqs``,
         which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()

@@ -189,6 +189,22 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_OVERREPRESENTED needs KVQ_FIND_PROFILE (the overrepresented sequences ride on the profile)");
         return nullptr;
     }
+    // the probes of KVQ_FIND_ADAPTERS ride behind the 20 bytes of kvq_find_opts: read only with the flag, and only when the size covers them
+    const uint8_t *probes[KVQ_ADAPT_MAX_PROBES] = { nullptr }; int32_t probe_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }, nprobes = 0;
+    if (flags & KVQ_FIND_ADAPTERS) {
+        if (!(flags & KVQ_FIND_PROFILE)) {
+            kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTERS needs KVQ_FIND_PROFILE (the adapter content rides on the profile)");
+            return nullptr;
+        }
+        const kvq_find_opts_adapters *oa = (const kvq_find_opts_adapters *)opts;
+        if (!opts || opts->size < sizeof(kvq_find_opts_adapters)) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: bad size"); return nullptr; }
+        if (oa->n_probes < 1 || oa->n_probes > KVQ_ADAPT_MAX_PROBES) {
+            kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTERS takes 1 to %d probes", KVQ_ADAPT_MAX_PROBES);
+            return nullptr;
+        }
+        nprobes = oa->n_probes;
+        for (int32_t k = 0; k < nprobes; k++) { probes[k] = oa->probes[k]; probe_lens[k] = oa->lens[k]; }
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -226,7 +242,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
               kvq_scan_set_profile(s, opts ? opts->cutoffs : nullptr, (flags & KVQ_FIND_PROFILE) ? opts->n_cutoffs : -1) ||
               kvq_scan_set_cycles(s, (flags & KVQ_FIND_CYCLES) ? 1 : 0) ||
               kvq_scan_set_read_stats(s, ((flags & KVQ_FIND_READ_STATS) ? KVQ_READ_STATS : 0) | ((flags & KVQ_FIND_DUPLICATION) ? KVQ_READ_DUPLICATION : 0)) ||
-              kvq_scan_set_overrepresented(s, (flags & KVQ_FIND_OVERREPRESENTED) ? 1 : 0))) {
+              kvq_scan_set_overrepresented(s, (flags & KVQ_FIND_OVERREPRESENTED) ? 1 : 0) ||
+              kvq_scan_set_adapters(s, probes, probe_lens, nprobes))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
     }
     const double tf1 = now_ms();
@@ -305,7 +322,8 @@ extern "C" kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
     kvq_find_opts o; memset(&o, 0, sizeof(o));
     o.size = (uint32_t)sizeof(o); o.flags = flags & ~(KVQ_FIND_PROFILE | KVQ_FIND_CYCLES);       // (the profile has cutoffs: kvq_findseqs_opts)
     // (... but for the per-read statistics, which need none: with them KVQ_FIND_PROFILE is a profile with no cutoffs)
-    if ((flags & (KVQ_FIND_READ_STATS | KVQ_FIND_DUPLICATION | KVQ_FIND_OVERREPRESENTED)) && (flags & KVQ_FIND_PROFILE)) o.flags = flags;
+    // (KVQ_FIND_ADAPTERS goes through as it is: this structure has no room for probes, and the flag without them is "bad size")
+    if ((flags & (KVQ_FIND_READ_STATS | KVQ_FIND_DUPLICATION | KVQ_FIND_OVERREPRESENTED | KVQ_FIND_ADAPTERS)) && (flags & KVQ_FIND_PROFILE)) o.flags = flags;
     return kvq_findseqs_opts(files, nfiles, seqs, seqlens, nseq, &o);
 }
 

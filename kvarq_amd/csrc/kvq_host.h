@@ -142,7 +142,7 @@ int kvq_comm_max_status(kvq_comm *c, unsigned long long mine, unsigned long long
 
 // An input pass: a kernel that every batch runs once over its exact record index and that adds to one device array, which the
 // tail of the scan brings to the host.  The cycles' array has the kernel's own scratch word behind the words that land.
-enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASSES };
+enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASS_ADAPT, KVQ_PASSES };
 typedef std::pair<hipEvent_t, hipEvent_t> KvqEventPair;
 struct KvqPass {
     bool on = false;
@@ -232,7 +232,8 @@ struct kvq_scan {
     int64_t rec_store_bytes = 0;                  // store bytes of the finished scan
     // the passes over a batch's exact record index (kvq_profile.hip; DESIGN section 13, "the lifecycle of an input pass"), in the
     // order they run: the profile of the input (kvq_scan_set_profile), the per-cycle counts beside it (kvq_scan_set_cycles) and what
-    // the individual reads look like (kvq_scan_set_read_stats) and the overrepresented sequences (kvq_scan_set_overrepresented).  All but
+    // the individual reads look like (kvq_scan_set_read_stats), the overrepresented sequences (kvq_scan_set_overrepresented) and the adapter content
+    // (kvq_scan_set_adapters).  All but
     // the first keep their buffers only while they are on
     KvqPass passes[KVQ_PASSES];
     int32_t prof_ncut = 0; uint8_t prof_cuts[KVQ_PROFILE_MAX_CUTOFFS] = { 0 };      // the profile's cutoffs
@@ -244,6 +245,8 @@ struct kvq_scan {
     // the overrepresented sequences: M, the slots of the table (the pass's array: KvqOverLayout), and the records the pass has seen
     // since it was last cleared -- the first M of them make the candidates
     uint64_t over_M = 0, over_slots = 0, over_seen = 0;
+    // the adapter content: the probes (kvq_scan_set_adapters; adapt_n == 0: off)
+    int32_t adapt_n = 0; uint8_t adapt_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t adapt_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
 };
 
 // kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal

@@ -1,5 +1,5 @@
-// kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16 and 17), host side: the profile, the
-// per-cycle counts, the per-read statistics and the overrepresented sequences as options of a scan object, the steps of their common lifecycle, the launch of
+// kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16, 17 and 18), host side: the profile, the
+// per-cycle counts, the per-read statistics, the overrepresented sequences and the adapter content as options of a scan object, the steps of their common lifecycle, the launch of
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
 #include <array>
@@ -76,6 +76,12 @@ static void over_off(kvq_scan *s)
     pass_off(s, s->passes[KVQ_PASS_OVER]);
 }
 
+static void adapt_off(kvq_scan *s)
+{
+    s->adapt_n = 0;
+    pass_off(s, s->passes[KVQ_PASS_ADAPT]);
+}
+
 // the device arrays of the passes that are on (and the duplication's table: a zero state block is level 0 with table 0 active) back to
 // zero: wherever the hit arena is cleared (reset_device_state), so that a replay, a rescan round and a file read again count every record once
 static int pass_clear(kvq_scan *s, int which)
@@ -134,6 +140,12 @@ static void passes_landed(kvq_scan *s)
         });
         if (!rows.empty()) memcpy(h.data() + KVQ_OVER_ROWS, rows.data(), rows.size() * sizeof(Row));
     }
+    if (s->passes[KVQ_PASS_ADAPT].on) {
+        // the words that are no sums: n and every m_k
+        std::vector<int64_t> &h = s->passes[KVQ_PASS_ADAPT].h;
+        h[KVQ_ADAPT_N] = s->adapt_n;
+        for (int k = 0; k < s->adapt_n; k++) h[KVQ_ADAPT_BLOCKS + (size_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = s->adapt_lens[k];
+    }
 }
 // what an accessor hands out: the copy of a pass that is on, of a finished scan
 static const int64_t *pass_result(const kvq_scan *s, int which)
@@ -153,7 +165,7 @@ extern "C" int32_t kvq_scan_set_profile(kvq_scan *s, const uint8_t *cutoffs, int
     int rc;
     kvq_clear_error();
     if ((rc = scan_idle(s, "kvq_scan_set_profile"))) return rc;
-    if (ncut < 0) { s->passes[KVQ_PASS_PROFILE].on = false; s->prof_ncut = 0; pass_off(s, s->passes[KVQ_PASS_CYCLES]); reads_off(s); over_off(s); return KVQ_OK; }
+    if (ncut < 0) { s->passes[KVQ_PASS_PROFILE].on = false; s->prof_ncut = 0; pass_off(s, s->passes[KVQ_PASS_CYCLES]); reads_off(s); over_off(s); adapt_off(s); return KVQ_OK; }
     if (ncut > KVQ_PROFILE_MAX_CUTOFFS || (ncut > 0 && !cutoffs)) {
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_profile: at most %d cutoffs", KVQ_PROFILE_MAX_CUTOFFS);
         return KVQ_ERR_RUNTIME;
@@ -347,3 +359,45 @@ static int over_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
 }
 
 extern "C" const int64_t *kvq_scan_over(const kvq_scan *s) { return pass_result(s, KVQ_PASS_OVER); }
+
+// ---- adapter content ----
+extern "C" int64_t kvq_adapt_len(void) { return KVQ_ADAPT_WORDS; }
+
+extern "C" int32_t kvq_scan_set_adapters(kvq_scan *s, const uint8_t *const *probes, const int32_t *lens, int32_t n)
+{
+    int rc;
+    kvq_clear_error();
+    if ((rc = scan_idle(s, "kvq_scan_set_adapters"))) return rc;
+    if (n == 0) { adapt_off(s); return KVQ_OK; }
+    if (!s->passes[KVQ_PASS_PROFILE].on) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_adapters: the scan keeps no profile (the adapter content rides on its record set and index: kvq_scan_set_profile first)");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (!adapt_probes_ok("kvq_scan_set_adapters", probes, lens, n)) return KVQ_ERR_RUNTIME;
+    if ((rc = pass_make(s->passes[KVQ_PASS_ADAPT], (size_t)KVQ_ADAPT_WORDS * 8, KVQ_ADAPT_WORDS, (size_t)KVQ_ADAPT_WORDS * 8))) { adapt_off(s); return rc; }
+    s->adapt_n = n;
+    memset(s->adapt_lens, 0, sizeof(s->adapt_lens)); memset(s->adapt_probes, 0, sizeof(s->adapt_probes));
+    for (int32_t k = 0; k < n; k++) { s->adapt_lens[k] = (uint8_t)lens[k]; memcpy(s->adapt_probes[k], probes[k], (size_t)lens[k]); }
+    return pass_clear(s, KVQ_PASS_ADAPT);
+}
+
+// the pass over the R records of a batch, behind its other passes: the probes go along by value, as 2-bit codes
+static int adapt_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    KvqAdaptProbes P; memset(&P, 0, sizeof(P));
+    P.n = (uint32_t)s->adapt_n;
+    for (int k = 0; k < s->adapt_n; k++) {
+        const uint32_t m = s->adapt_lens[k];
+        for (uint32_t i = 0; i < m; i++) P.code[k] |= (unsigned long long)((s->adapt_probes[k][i] >> 1) & 3u) << (2u * i);
+        P.mask[k] = m >= 32u ? ~0ull : (1ull << (2u * m)) - 1ull;               // (no shift by 64)
+        P.m[k] = m;
+    }
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
+    hipLaunchKernelGGL(kvq_adapt_kernel(P.n), dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
+                       (uint32_t)R, P, s->passes[KVQ_PASS_ADAPT].d.as<unsigned long long>());
+    KVQ_HIP(hipGetLastError());
+    return KVQ_OK;
+}
+
+extern "C" const int64_t *kvq_scan_adapters(const kvq_scan *s) { return pass_result(s, KVQ_PASS_ADAPT); }

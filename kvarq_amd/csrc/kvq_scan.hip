@@ -561,7 +561,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
     // the profile: every batch once, by its first pass (the redo of a batch that failed validation leaves it alone, and so does
     // the redo of skipped tiles), from the exact index -- the exhaustive pass's where the batch has one; a seeded batch waits
     // on the host once for its own.  In front of the closing event: what guards the batch's text guards this pass too
-    // (the cycles, the per-read statistics and the overrepresented sequences are on only beside the profile: right behind it, from the same index)
+    // (the cycles, the per-read statistics, the overrepresented sequences and the adapter content are on only beside the profile: right behind it, from the same index)
     if (s->passes[KVQ_PASS_PROFILE].on && !exhaustive_only) {
         if (B.nrec < 0 && (rc = index_records(s, B))) return rc;
         for (int i = 0; i < KVQ_PASSES && B.nrec > 0; i++) {
@@ -574,6 +574,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
             case KVQ_PASS_CYCLES: rc = cycles_enqueue(s, d_data, (uint64_t)B.nrec); break;
             case KVQ_PASS_READS: rc = reads_enqueue(s, d_data, (uint64_t)B.nrec); break;
             case KVQ_PASS_OVER: rc = over_enqueue(s, d_data, (uint64_t)B.nrec); break;
+            case KVQ_PASS_ADAPT: rc = adapt_enqueue(s, d_data, (uint64_t)B.nrec); break;
             }
             if (rc) return rc;
             KVQ_HIP(hipEventRecord(p.ev.back().second, s->stream));

@@ -1,6 +1,7 @@
-// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16 and 17): the
-// definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records and kvq_over_records in plain C++ (test infrastructure,
-// never a fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record walk serve all four.
+// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16, 17 and 18): the
+// definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records, kvq_over_records and kvq_adapt_records in plain C++
+// (test infrastructure, never a fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record
+// walk serve all five.
 #include "../../include/kvarq_hip.h"
 #include "kvq_dup_hash.h"
 #include <algorithm>
@@ -154,6 +155,56 @@ extern "C" int32_t kvq_over_host(const uint8_t *text, int64_t nbytes, const int6
             row[KVQ_OVER_ROW_KEY + i] = (int64_t)w;
         }
     }
+    return KVQ_OK;
+}
+
+// what kvq_scan_set_adapters and kvq_adapt_host ask of their probes: 1 .. KVQ_ADAPT_MAX_PROBES of them, KVQ_ADAPT_MIN_PROBE ..
+// KVQ_ADAPT_MAX_PROBE bytes each, every byte an upper-case A C G T
+static bool adapt_probes_ok(const char *who, const uint8_t *const *probes, const int32_t *lens, int32_t n)
+{
+    bool ok = n >= 1 && n <= KVQ_ADAPT_MAX_PROBES && probes && lens;
+    for (int32_t k = 0; ok && k < n; k++) {
+        ok = probes[k] && lens[k] >= KVQ_ADAPT_MIN_PROBE && lens[k] <= KVQ_ADAPT_MAX_PROBE;
+        for (int32_t i = 0; ok && i < lens[k]; i++) ok = probes[k][i] == 'A' || probes[k][i] == 'C' || probes[k][i] == 'G' || probes[k][i] == 'T';
+    }
+    if (!ok) kvq_set_error(KVQ_ERR_RUNTIME, "%s: 1 to %d probes of %d to %d bytes, every byte one of upper-case A C G T", who,
+                           KVQ_ADAPT_MAX_PROBES, KVQ_ADAPT_MIN_PROBE, KVQ_ADAPT_MAX_PROBE);
+    return ok;
+}
+
+extern "C" int32_t kvq_adapt_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                  const uint8_t *const *probes, const int32_t *lens, int32_t n, int64_t *out)
+{
+    if (!twin_args("kvq_adapt_host", out != nullptr, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    if (!adapt_probes_ok("kvq_adapt_host", probes, lens, n)) return KVQ_ERR_RUNTIME;
+    out[KVQ_ADAPT_N] = n;
+    for (int32_t k = 0; k < n; k++) out[KVQ_ADAPT_BLOCKS + (int64_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = lens[k];
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t, int64_t) {
+        const uint8_t *line = text + n0 + 1;
+        int64_t L = n1 - n0 - 1;
+        if (L > 0 && line[L - 1] == '\r') L--;                                 // a trailing '\r' is not part of its line
+        int64_t clip = L;
+        bool full = false, tailed = false;
+        for (int32_t k = 0; k < n; k++) {
+            int64_t *const blk = out + KVQ_ADAPT_BLOCKS + (int64_t)k * KVQ_ADAPT_BLOCK_WORDS;
+            const int64_t m = lens[k];
+            int64_t first = -1, tail = -1;
+            for (int64_t p = 0; first < 0 && p + m <= L; p++) if (!memcmp(line + p, probes[k], (size_t)m)) first = p;
+            for (int64_t t = std::min(m - 1, L); first < 0 && tail < 0 && t >= KVQ_ADAPT_MIN_TAIL; t--)
+                if (!memcmp(line + L - t, probes[k], (size_t)t)) tail = t;
+            if (first >= 0) {
+                full = true; clip = std::min(clip, first);
+                blk[KVQ_ADAPT_B_FIRST]++;
+                blk[first < KVQ_ADAPT_POSITIONS ? KVQ_ADAPT_B_FIRST_BINS + first : (int64_t)KVQ_ADAPT_B_BEYOND]++;
+            } else if (tail >= 0) {
+                tailed = true; clip = std::min(clip, L - tail);
+                blk[KVQ_ADAPT_B_TAIL]++; blk[KVQ_ADAPT_B_TAIL_BINS + tail]++;
+            }
+        }
+        out[KVQ_ADAPT_RECORDS]++;
+        out[full ? KVQ_ADAPT_WITH_FULL : KVQ_ADAPT_TAIL_ONLY] += full || tailed;
+        out[KVQ_ADAPT_CLIP + std::min<int64_t>(clip, KVQ_ADAPT_CLIP_BINS - 1)]++;
+    });
     return KVQ_OK;
 }
 

@@ -208,6 +208,13 @@ def findseqs(fname, sequences, *, inflate='host', **options):
     the whole input (``Profile.overrepresented``).  Without ``profile`` it means a
     profile with no cutoffs.
 
+    adapters=True / {name: bytes} / [bytes, ...]: that profile also tells how much of the input is adapter
+    and from which cycle on (``Profile.adapters``): per read and probe the first full
+    occurrence of the probe on the bases line, else the longest prefix of the probe (6 bases and more)
+    that ends the line, and the histogram of the length an adapter clip would leave.  True: the entries
+    of ``profile.KNOWN_SOURCES`` that are bytes.  1 to 8 probes of 8 to 32 upper-case A C G T, matched
+    byte for byte.  Without ``profile`` it means a profile with no cutoffs.
+
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
     no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are
@@ -255,7 +262,8 @@ def findseqs(fname, sequences, *, inflate='host', **options):
 
     # ctypes releases the GIL for the duration of the call (workhorse.c:1377-1408)
     t_0 = time.perf_counter()
-    h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.byref(opt.find_opts(INFLATE_FLAGS[inflate])))
+    fo = opt.find_opts(INFLATE_FLAGS[inflate])        # (kvq_find_opts, or the longer structure that begins with it)
+    h = L.kvq_findseqs_opts(farr, len(bfiles), sarr, lens, n, C.cast(C.byref(fo), C.POINTER(_lib.FindOpts)))
     t_1 = time.perf_counter()
     try:
         if h:
@@ -281,7 +289,7 @@ def findseqs(fname, sequences, *, inflate='host', **options):
             out['records'] = scan_records(L, h, as_str)
         if opt.profile is not None:
             from . import profile as profile_
-            out['profile'] = profile_.from_scan(L, h)
+            out['profile'] = profile_.from_scan(L, h, adapters=(opt.adapter_names, opt.adapters))
         return out
     finally:
         if h:

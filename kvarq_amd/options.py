@@ -1,6 +1,6 @@
 """
 The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
-``duplication``, ``overrepresented`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+``duplication``, ``overrepresented``, ``adapters`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
 everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
 """
 import ctypes as C
@@ -13,15 +13,20 @@ class ScanOptions(object):
     (``profile.as_cutoffs``; True: ``amin``, or the configured Amin; None: no profile) -- a list of byte values here;
     ``cycles``: the per-cycle counts beside it; ``read_stats``: the mode bits of kvq_scan_set_read_stats for ``per_read`` and
     ``duplication``; ``overrepresented``: the overrepresented sequences; ``long_mode``: the mode of kvq_scan_set_long_reads
-    for ``long_reads`` (False, True or 'auto').
-    ``cycles``, ``per_read``, ``duplication`` or ``overrepresented`` without ``profile`` mean a profile with no cutoffs."""
+    for ``long_reads`` (False, True or 'auto'); ``adapters``: the probes of the adapter content (``profile.as_adapters``: True,
+    a mapping name -> bytes or a list of bytes; None or False: off) -- ``adapter_names`` and ``adapters``, a list of bytes, here.
+    ``cycles``, ``per_read``, ``duplication``, ``overrepresented`` or ``adapters`` without ``profile`` mean a profile with no cutoffs."""
 
     def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, overrepresented=False,
-                 amin=None):
+                 adapters=None, amin=None):
         self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
         self.records, self.cycles, self.overrepresented = bool(records), bool(cycles), bool(overrepresented)
         self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
-        if (self.cycles or self.read_stats or self.overrepresented) and profile is None:
+        self.adapter_names, self.adapters = None, None
+        if adapters is not None and adapters is not False:
+            from .profile import as_adapters
+            self.adapter_names, self.adapters = as_adapters(adapters)
+        if (self.cycles or self.read_stats or self.overrepresented or self.adapters) and profile is None:
             profile = ()
         self.profile = None
         if profile is not None:
@@ -35,7 +40,15 @@ class ScanOptions(object):
             flags |= (_lib.FIND_PROFILE | (_lib.FIND_CYCLES if self.cycles else 0) | (_lib.FIND_READ_STATS if self.read_stats & _lib.READ_STATS else 0) |
                       (_lib.FIND_DUPLICATION if self.read_stats & _lib.READ_DUPLICATION else 0) | (_lib.FIND_OVERREPRESENTED if self.overrepresented else 0))
         cuts = self.profile or ()
-        return _lib.FindOpts(C.sizeof(_lib.FindOpts), flags, len(cuts), (C.c_uint8 * 8)(*cuts))
+        base = _lib.FindOpts(C.sizeof(_lib.FindOpts), flags, len(cuts), (C.c_uint8 * 8)(*cuts))
+        if not self.adapters:
+            return base
+        # (the probes ride behind the 20 bytes, which stay what they are whenever the adapters are off)
+        base.size, base.flags = C.sizeof(_lib.FindOptsAdapters), flags | _lib.FIND_ADAPTERS
+        o = _lib.FindOptsAdapters(base, len(self.adapters), (C.c_uint8 * 8)(*[len(p) for p in self.adapters]))
+        for k, p in enumerate(self.adapters):
+            C.memmove(o.probes[k], p, len(p))
+        return o
 
     def setters(self):
         """the kvq_scan_set_* calls of a new scan handle, in order: (name, arguments behind the handle)"""
@@ -48,6 +61,9 @@ class ScanOptions(object):
                 calls.append(('kvq_scan_set_read_stats', (self.read_stats,)))
             if self.overrepresented:
                 calls.append(('kvq_scan_set_overrepresented', (1,)))
+            if self.adapters:
+                n = len(self.adapters)
+                calls.append(('kvq_scan_set_adapters', ((C.c_char_p * n)(*self.adapters), (C.c_int32 * n)(*[len(p) for p in self.adapters]), n)))
         if self.long_mode:
             calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
         return calls

@@ -23,6 +23,12 @@ input and a label of where it may come from (``KNOWN_SOURCES``); ``--overreprese
 the sequences among the first 2^18 records: a sequence that first shows up behind them is not found, which in a file that is
 not sorted has a probability of e^-262 at a share of 0.1 %.
 
+With ``adapters=`` it tells HOW MUCH OF THE INPUT IS ADAPTER, AND FROM WHICH CYCLE ON: per read and probe
+the first full occurrence of the probe on the bases line, else the longest prefix of the probe, 6 bases and more, that ends the
+line (read-through whose adapter the read cuts off), and the histogram of the length an adapter clip would leave
+(``Profile.adapters``, ``Profile.adapter_content()`` and what follows it); ``--adapters [NAME=SEQ ...]`` prints them.  Matching
+is on bytes, without mismatches: 1 to 8 probes of 8 to 32 upper-case A C G T.
+
 Out of scope: profiles across ranks, and what ``Fastq`` guesses by default.
 """
 import collections
@@ -54,6 +60,13 @@ DUP_BOUNDS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)   
 OVER_HEADER = ('records_limit', 'slots', 'keyed', 'unkeyed', 'candidates', 'counted', 'listed')
 OVER_ROWS, OVER_ROW_WORDS, OVER_MAX_ROWS = 8, 11, 1000
 OVER_LEN = OVER_ROWS + OVER_MAX_ROWS * OVER_ROW_WORDS
+
+# the adapter content (include/kvarq_hip.h: kvq_adapt_len()): the header words, a block per probe, the clip histogram
+ADAPT_N, ADAPT_RECORDS, ADAPT_WITH_FULL, ADAPT_TAIL_ONLY, ADAPT_BLOCKS, ADAPT_BLOCK_WORDS = 0, 1, 2, 3, 8, 1064
+ADAPT_B_M, ADAPT_B_FIRST, ADAPT_B_BEYOND, ADAPT_B_TAIL, ADAPT_B_FIRST_BINS, ADAPT_B_TAIL_BINS = 0, 1, 2, 3, 8, 1032
+ADAPT_MAX_PROBES, ADAPT_MIN_PROBE, ADAPT_MAX_PROBE, ADAPT_MIN_TAIL, ADAPT_POSITIONS = 8, 8, 32, 6, 1024
+ADAPT_CLIP, ADAPT_CLIP_BINS = ADAPT_BLOCKS + ADAPT_MAX_PROBES * ADAPT_BLOCK_WORDS, 1025
+ADAPT_LEN = ADAPT_CLIP + ADAPT_CLIP_BINS
 
 Overrepresented = collections.namedtuple('Overrepresented', 'sequence count share hash source')
 
@@ -92,6 +105,66 @@ def source_of(sequence, sources=None):
             if probe and (probe in sequence or probe.translate(_COMPLEMENT)[::-1] in sequence):
                 return label
     return None
+
+
+def as_adapters(adapters):
+    """the probes of the adapter content as ``(names, probes)``, two lists: ``True``: the entries of ``KNOWN_SOURCES`` whose
+    value is bytes, in their order; a mapping name -> bytes; or a list of bytes (named 'probe 0', 'probe 1', ...).  1 to 8
+    probes of 8 to 32 bytes, every byte one of upper-case A C G T -- ValueError otherwise"""
+    if adapters is True:
+        adapters = collections.OrderedDict((k, v) for k, v in KNOWN_SOURCES.items() if isinstance(v, (bytes, bytearray)))
+    if isinstance(adapters, (str, bytes, bytearray)):
+        adapters = [adapters]
+    if hasattr(adapters, 'items'):
+        names, probes = [str(k) for k in adapters], list(adapters.values())
+    else:
+        probes = list(adapters)
+        names = ['probe %d' % k for k in range(len(probes))]
+    probes = [p.encode('latin-1') if isinstance(p, str) else bytes(p) for p in probes]
+    if not 1 <= len(probes) <= ADAPT_MAX_PROBES:
+        raise ValueError('1 to %d adapter probes' % ADAPT_MAX_PROBES)
+    for p in probes:
+        if not ADAPT_MIN_PROBE <= len(p) <= ADAPT_MAX_PROBE or p.strip(b'ACGT'):
+            raise ValueError('an adapter probe is %d to %d bytes, every byte one of upper-case A C G T: %r' % (ADAPT_MIN_PROBE, ADAPT_MAX_PROBE, p))
+    return names, probes
+
+
+class Adapters(object):
+    """the adapter content of a profile (kvq_scan_adapters; the definition: include/kvarq_hip.h): ``names`` and ``probes`` (bytes)
+    of the n probes; ``first`` (n x 1024): the records whose first full occurrence of probe k starts at position p, ``beyond``
+    (n): those where it starts at 1024 and further; ``tail`` (n x 32): the records without a full occurrence of probe k whose
+    line ends with its first t bases (t >= 6, the longest such t); ``clip`` (1025): the records by the length an adapter clip
+    would leave, 1024 and more in the last bin; ``records``, ``with_adapter`` (records with a full occurrence of any probe),
+    ``tail_only`` (records with none but a tail match); ``words``: the flat array"""
+
+    def __init__(self, words, names=None, probes=None):
+        self.words = w = np.array(words, dtype=np.int64)
+        assert w.shape == (ADAPT_LEN,)
+        n = int(w[ADAPT_N])
+        blocks = w[ADAPT_BLOCKS:ADAPT_CLIP].reshape(ADAPT_MAX_PROBES, ADAPT_BLOCK_WORDS)[:n]
+        self.lengths = [int(v) for v in blocks[:, ADAPT_B_M]]
+        self.names = list(names) if names is not None else ['probe %d' % k for k in range(n)]
+        self.probes = [bytes(p) for p in probes] if probes is not None else [None] * n
+        assert len(self.names) == n and len(self.probes) == n
+        self.records, self.with_adapter, self.tail_only = int(w[ADAPT_RECORDS]), int(w[ADAPT_WITH_FULL]), int(w[ADAPT_TAIL_ONLY])
+        self.found, self.beyond, self.tailed = blocks[:, ADAPT_B_FIRST], blocks[:, ADAPT_B_BEYOND], blocks[:, ADAPT_B_TAIL]
+        self.first = blocks[:, ADAPT_B_FIRST_BINS:ADAPT_B_FIRST_BINS + ADAPT_POSITIONS]
+        self.tail = blocks[:, ADAPT_B_TAIL_BINS:ADAPT_B_TAIL_BINS + 32]
+        self.clip = w[ADAPT_CLIP:ADAPT_CLIP + ADAPT_CLIP_BINS]
+
+    def __eq__(self, other):
+        return isinstance(other, Adapters) and bool((self.words == other.words).all())
+
+    def __ne__(self, other):
+        return not self == other
+
+    def as_dict(self):
+        def bins(h):
+            return {int(b): int(h[b]) for b in np.nonzero(h)[0]}
+        return {'records': self.records, 'with_adapter': self.with_adapter, 'tail_only': self.tail_only, 'clip': bins(self.clip),
+                'probes': [{'name': self.names[k], 'sequence': self.probes[k].decode('latin-1') if self.probes[k] is not None else None,
+                            'length': self.lengths[k], 'found': int(self.found[k]), 'beyond': int(self.beyond[k]), 'tailed': int(self.tailed[k]),
+                            'first': bins(self.first[k]), 'tail': bins(self.tail[k])} for k in range(len(self.names))]}
 
 
 def profile_len(ncut):
@@ -185,10 +258,13 @@ class Profile(object):
     ``over``: the flat array of kvq_scan_over (kvq_over_len() words) when the scan took it, else None -- ``over_info``: its
     header words by name (``OVER_HEADER``), ``overrepresented``: its rows in their canonical order (count descending, ties by
     hash ascending) as named tuples ``(sequence: bytes, count, share = count / keyed, hash, source)``, ``source`` the label
-    of ``source_of`` under ``sources`` (None: ``KNOWN_SOURCES``)"""
+    of ``source_of`` under ``sources`` (None: ``KNOWN_SOURCES``);
+    ``adapters``: the adapter content (``Adapters``: ``names``, ``probes``, ``first``, ``tail``, ``beyond``, ``clip``, ``records``,
+    ``with_adapter``, ``tail_only``) when the scan took it, else None"""
 
-    def __init__(self, words, cutoffs, cycles=None, reads=None, dup=None, over=None, sources=None):
+    def __init__(self, words, cutoffs, cycles=None, reads=None, dup=None, over=None, sources=None, adapters=None):
         self.cutoffs = list(cutoffs)
+        self.adapters = adapters
         self.over = self.over_info = self.overrepresented = None
         if over is not None:
             self.over = np.array(over, dtype=np.int64)
@@ -222,6 +298,8 @@ class Profile(object):
         if not (isinstance(other, Profile) and self.cutoffs == other.cutoffs and (self.words == other.words).all()):
             return False
         if self.duplication != other.duplication or self.over_info != other.over_info:
+            return False
+        if (self.adapters is None) != (other.adapters is None) or (self.adapters is not None and self.adapters != other.adapters):
             return False
         if self.over is not None and [r[:4] for r in self.overrepresented] != [r[:4] for r in other.overrepresented]:
             return False                                  # (the labels are the host's reading of the rows, not a part of them)
@@ -465,6 +543,56 @@ class Profile(object):
                                              r.source or 'no known source'))
         return lines
 
+    # -- adapter content -----------------------------------------------------------
+
+    def _adapters(self):
+        if self.adapters is None:
+            raise ValueError('this profile was taken without adapters=')
+        return self.adapters
+
+    def adapter_content(self, k=None):
+        """(1024,): per cycle p, the share of all records whose first full occurrence of probe ``k`` (an index or a name) starts
+        at p or before it -- FastQC's curve; ``k`` None: the sum over the probes.  nan without records"""
+        a = self._adapters()
+        if k is None:
+            first = a.first.sum(axis=0)
+        else:
+            first = a.first[a.names.index(k) if not isinstance(k, int) else k]
+        return _share(np.cumsum(first), a.records)
+
+    def adapter_share(self):
+        """the share of the records that hold a full occurrence of any probe; nan without records"""
+        a = self._adapters()
+        return a.with_adapter / float(a.records) if a.records else float('nan')
+
+    def clipped_share(self):
+        """the share of the records an adapter clip would shorten: those with a full occurrence of a probe or, failing that,
+        with a tail match; nan without records"""
+        a = self._adapters()
+        return (a.with_adapter + a.tail_only) / float(a.records) if a.records else float('nan')
+
+    def clip_quantile(self, q):
+        """the smallest length whose cumulative count reaches ``q`` (0 .. 1) of the records by the length an adapter clip would
+        leave (1024: that and more); nan without records"""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError('a quantile lies in 0 .. 1')
+        a = self._adapters()
+        cum = np.cumsum(a.clip)
+        return float((cum >= max(q * cum[-1], 1)).argmax()) if cum[-1] else float('nan')
+
+    def adapter_lines(self):
+        """the adapter part of the command line: the shares, the quantiles of the clipped length, then a line per probe"""
+        a = self._adapters()
+        lines = ['adapters: records=%d with_adapter=%d (%.4f) tail_only=%d clipped share %.4f'
+                 % (a.records, a.with_adapter, self.adapter_share(), a.tail_only, self.clipped_share()),
+                 'clipped length: %s' % ' '.join('Q%d=%g' % (int(q * 100), self.clip_quantile(q)) for q in (0.1, 0.25, 0.5, 0.75, 0.9))]
+        for k, name in enumerate(a.names):
+            at = np.nonzero(a.first[k])[0]
+            lines.append('%s %s: found=%d (%.4f) first cycle=%s beyond=%d tails=%d'
+                         % (name, a.probes[k].decode('latin-1') if a.probes[k] is not None else '?', int(a.found[k]),
+                            int(a.found[k]) / float(a.records) if a.records else 0.0, int(at[0]) if at.size else '-', int(a.beyond[k]), int(a.tailed[k])))
+        return lines
+
     def summary(self):
         lines = ['records=%d mismatched=%d longest=%d' % (self.records, self.mismatched, self.longest)]
         lo_, hi = self.score_range()
@@ -500,29 +628,35 @@ class Profile(object):
             d['duplication'] = dict(self.duplication, bounds=list(DUP_BOUNDS))
         if self.over is not None:
             d['overrepresented'] = dict(self.over_info, rows=[dict(r._asdict(), sequence=r.sequence.decode('latin-1')) for r in self.overrepresented])
+        if self.adapters is not None:
+            d['adapters'] = self.adapters.as_dict()
         return d
 
 
-def from_scan(L, h, sources=None):
-    """the profile of a finished scan object (kvq_scan_profile), None when it keeps none; ``sources``: as for ``Profile``"""
+def from_scan(L, h, sources=None, adapters=None):
+    """the profile of a finished scan object (kvq_scan_profile), None when it keeps none; ``sources``: as for ``Profile``;
+    ``adapters``: ``(names, probes)`` of the scan's adapter probes (``ScanOptions``), which the flat array does not hold"""
     cuts = (C.c_uint8 * MAX_CUTOFFS)()
     n = L.kvq_scan_profile_cutoffs(h, cuts)
     ptr = L.kvq_scan_profile(h)
     if n < 0 or not ptr:
         return None
     cyc, reads, dup, over = L.kvq_scan_cycles(h), L.kvq_scan_reads(h), L.kvq_scan_dup(h), L.kvq_scan_over(h)
+    ada = L.kvq_scan_adapters(h)
+    names, probes = adapters if adapters is not None else (None, None)
     return Profile(np.ctypeslib.as_array(ptr, shape=(profile_len(n),)).copy(), list(cuts)[:n],
                    np.ctypeslib.as_array(cyc, shape=(CYCLES_LEN,)).copy() if cyc else None,
                    np.ctypeslib.as_array(reads, shape=(READS_LEN,)).copy() if reads else None,
                    np.ctypeslib.as_array(dup, shape=(DUP_LEN,)).copy() if dup else None,
-                   np.ctypeslib.as_array(over, shape=(OVER_LEN,)).copy() if over else None, sources)
+                   np.ctypeslib.as_array(over, shape=(OVER_LEN,)).copy() if over else None, sources,
+                   Adapters(np.ctypeslib.as_array(ada, shape=(ADAPT_LEN,)).copy(), names, probes) if ada else None)
 
 
 def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False, duplication=False, slots=0, overrepresented=False,
-                 over_records=0, sources=None):
+                 over_records=0, sources=None, adapters=None):
     """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host; per_read / duplication: and kvq_reads_host, with a
     table of ``slots`` slots, 0: the default; overrepresented: and kvq_over_host, with the first ``over_records`` records
-    making the candidates, 0: the default) over a text in host memory; chunk_off None: the reader's chunk cuts"""
+    making the candidates, 0: the default; adapters: and kvq_adapt_host, with the probes of ``as_adapters``) over a text in host memory; chunk_off None: the reader's chunk cuts"""
     from . import scan
     cuts = as_cutoffs(cutoffs)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
@@ -551,13 +685,31 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False,
         if _lib.lib().kvq_over_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
                                     int(over_records), over.ctypes.data_as(C.POINTER(C.c_int64))):
             raise RuntimeError(_lib.last_error()[1])
-    return Profile(out, cuts, cyc, reads, dup, over, sources)
+    ada = None
+    if adapters is not None and adapters is not False:
+        ada = adapt_host(arr, adapters, co)
+    return Profile(out, cuts, cyc, reads, dup, over, sources, ada)
+
+
+def adapt_host(text, adapters, chunk_off=None):
+    """the CPU twin of the adapter content alone (kvq_adapt_host) over a text in host memory: an ``Adapters``"""
+    from . import scan
+    names, probes = as_adapters(adapters)
+    arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
+    co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
+    n = len(probes)
+    words = np.zeros(ADAPT_LEN, dtype=np.int64)
+    if _lib.lib().kvq_adapt_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+                                 (C.c_char_p * n)(*probes), (C.c_int32 * n)(*[len(p) for p in probes]), n, words.ctypes.data_as(C.POINTER(C.c_int64))):
+        raise RuntimeError(_lib.last_error()[1])
+    return Adapters(words, names, probes)
 
 
 def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
     per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication; ``overrepresented``:
-    with the overrepresented sequences, labelled from ``sources`` (None: ``KNOWN_SOURCES``); ``long_reads``: as for
+    with the overrepresented sequences, labelled from ``sources`` (None: ``KNOWN_SOURCES``); ``adapters``: with the adapter
+    content of these probes (``as_adapters``); ``long_reads``: as for
     ``engine.findseqs``, which takes the ``options``"""
     from . import engine
     p = engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)['profile']
@@ -578,8 +730,14 @@ def main(argv=None):
     ap.add_argument('--per-read', action='store_true', help='the per-read GC histogram in 5 %% steps with its mean, the quantiles of the per-read mean quality, the share of reads with any N')
     ap.add_argument('--duplication', action='store_true', help='how often the first 64 bases of the reads repeat: level, sample size and a line per count bin')
     ap.add_argument('--overrepresented', action='store_true', help='the sequences (first 64 bases) that make up 0.1 %% of the reads and more, among those of the first 2^18 records: count, share, known source')
+    ap.add_argument('--adapters', nargs='*', metavar='NAME=SEQ', help='the adapter content: how many reads hold each probe and from which cycle on, tails of 6 bases and more, the length a clip would leave; without arguments: the known adapters')
     a = ap.parse_args(argv)
     more = dict(cycles=a.cycles, per_read=a.per_read, duplication=a.duplication, overrepresented=a.overrepresented)
+    if a.adapters is not None:
+        for item in a.adapters:
+            if '=' not in item:
+                ap.error('--adapters takes NAME=SEQ')
+        more['adapters'] = collections.OrderedDict((i.split('=', 1)[0], i.split('=', 1)[1].encode('latin-1')) for i in a.adapters) if a.adapters else True
     p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
@@ -593,6 +751,8 @@ def main(argv=None):
         print('\n'.join(p.duplication_lines()))
     if a.overrepresented:
         print('\n'.join(p.overrepresented_lines()))
+    if a.adapters is not None:
+        print('\n'.join(p.adapter_lines()))
 
 
 if __name__ == '__main__':

@@ -92,11 +92,12 @@ class Scanner(object):
 
     def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, **options):
         self.table = table
-        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented (``options.ScanOptions``), set on the
+        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters (``options.ScanOptions``), set on the
         # scan handle once and kept across reset
         opt = ScanOptions(amin=bytes([table.config.Amin & 0xFF]), **options)
         self.records, self.profile, self.cycles, self.read_stats, self.long_reads = opt.records, opt.profile, opt.cycles, opt.read_stats, opt.long_reads
         self.overrepresented = opt.overrepresented
+        self.adapters, self.adapter_names = opt.adapters, opt.adapter_names
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
@@ -188,7 +189,7 @@ class Scanner(object):
                 out['records'] = scan_records(L, self.h)      # the record of every hit (bytes), in the order of ``hits``
         if self.profile is not None:
             from . import profile as profile_
-            out['profile'] = profile_.from_scan(L, self.h)
+            out['profile'] = profile_.from_scan(L, self.h, adapters=(self.adapter_names, self.adapters))
             out['profile_kernel_ms'] = L.kvq_scan_profile_kernel_ms(self.h)
             if self.cycles:
                 out['cycles_kernel_ms'] = L.kvq_scan_cycles_kernel_ms(self.h)
@@ -196,6 +197,8 @@ class Scanner(object):
                 out['reads_kernel_ms'] = L.kvq_scan_reads_kernel_ms(self.h)
             if self.overrepresented:
                 out['over_kernel_ms'] = L.kvq_scan_over_kernel_ms(self.h)
+            if self.adapters:
+                out['adapt_kernel_ms'] = L.kvq_scan_adapt_kernel_ms(self.h)
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
