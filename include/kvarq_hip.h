@@ -775,6 +775,17 @@ int64_t kvq_bam_to_fastq_host(const uint8_t *inflated, int64_t n, int32_t n_ref,
  * (kvq_last_error as above), -2 on other errors.  Blocking; *report (may be NULL) as kvq_bam_last_report */
 int64_t kvq_bam_to_fastq_device(const void *d_in, int64_t n, int32_t n_ref, int64_t first_record, void *d_out, int64_t cap,
                                 int64_t segment_bytes, kvq_bam_report *report);
+/* One run, as the route takes a file: p[0, n) is a prefix of a stream that ends at limit >= n (both relative to p).  Returns
+ * the text bytes of the records that lie wholly inside the prefix; *end (may be NULL): where the chain left the prefix, n or
+ * the offset of the record the prefix ends inside (what the route carries to the next run).  -1 at a malformed record (*end:
+ * its offset; kvq_last_error as above; a rule that shows in the bytes there are is not waited for), -2 on bad arguments or
+ * other errors.  kvq_bam_to_fastq_host / _device are these with limit = n (and out_off = 0).  The device run writes its text
+ * to d_out + out_off, d_out holding cap bytes, when out_off + text <= cap, and no other byte of d_out; it reads no byte of
+ * d_p behind n. */
+int64_t kvq_bam_run_host(const uint8_t *p, int64_t n, int64_t limit, int32_t n_ref, int64_t first_record, uint8_t *out, int64_t cap,
+                         int64_t *end);
+int64_t kvq_bam_run_device(const void *d_p, int64_t n, int64_t limit, int32_t n_ref, int64_t first_record, void *d_out, int64_t out_off,
+                           int64_t cap, int64_t segment_bytes, int64_t *end, kvq_bam_report *report);
 
 const char *kvq_version(void);
 

@@ -211,6 +211,8 @@ PROTOTYPES = {
     'kvq_bam_header_host': (i64, [vp, i64, P(i32)]),
     'kvq_bam_to_fastq_host': (i64, [vp, i64, i32, i64, vp, i64, P(i64)]),
     'kvq_bam_to_fastq_device': (i64, [vp, i64, i32, i64, vp, i64, i64, P(BamReport)]),
+    'kvq_bam_run_host': (i64, [vp, i64, i64, i32, i64, vp, i64, P(i64)]),
+    'kvq_bam_run_device': (i64, [vp, i64, i64, i32, i64, vp, i64, i64, i64, P(i64), P(BamReport)]),
     'kvq_version': (cp, []),
 }
 

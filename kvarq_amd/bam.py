@@ -142,6 +142,39 @@ def to_fastq_device(data, segment_bytes=None):
             L.kvq_device_free(d_out)
 
 
+def run_host(data, n, n_ref, first_record, limit=None):
+    """one run as the route takes it (kvq_bam_run_host): ``data[:n]`` is a prefix of a stream that ends at ``limit``
+    (None: ``len(data)``).  Returns (text, end): the text of the records wholly inside the prefix, and where the chain
+    left it.  BamError at a malformed record."""
+    data = bytes(data)
+    limit = len(data) if limit is None else limit
+    L = _lib.lib()
+    end = C.c_int64(-1)
+    t = L.kvq_bam_run_host(data, n, limit, n_ref, first_record, None, 0, C.byref(end))
+    if t < 0:
+        _raise()
+    out = C.create_string_buffer(max(1, t))
+    if L.kvq_bam_run_host(data, n, limit, n_ref, first_record, out, t, C.byref(end)) != t:
+        _raise()
+    return out.raw[:t], end.value
+
+
+def run_device(d_p, n, limit, n_ref, first_record, d_out, out_off, cap, segment_bytes=None):
+    """kvq_bam_run_device on buffers the caller holds in device memory (kvq_device_alloc).  Returns (text bytes, end,
+    report dict); BamError at a malformed record (``.end`` and ``.report`` on the exception)."""
+    end = C.c_int64(-1)
+    rep = _lib.BamReport()
+    t = _lib.lib().kvq_bam_run_device(d_p, n, limit, n_ref, first_record, d_out, out_off, cap, int(segment_bytes or 0),
+                                      C.byref(end), C.byref(rep))
+    if t < 0:
+        try:
+            _raise()
+        except BamError as e:
+            e.end, e.report = end.value, rep.as_dict()
+            raise
+    return t, end.value, rep.as_dict()
+
+
 def _first_written_length(path):
     """l_seq of the first record that writes text (0 when there is none), read record by record from the front"""
     with gzip.open(path, 'rb') as fd:

@@ -226,57 +226,78 @@ extern "C" int64_t kvq_bam_header_host(const uint8_t *inflated, int64_t n, int32
     return o;
 }
 
-extern "C" int64_t kvq_bam_to_fastq_host(const uint8_t *inflated, int64_t n, int32_t n_ref, int64_t first_record, uint8_t *out, int64_t cap,
-                                         int64_t *consumed)
+// One run as the route takes a file: p[0, n) a prefix of a stream that ends at limit.  The host twin walks the chain itself;
+// the device run is bam_run_find and bam_run_emit as BamProducer calls them.  kvq_bam_to_fastq_* are these with limit = n.
+extern "C" int64_t kvq_bam_run_host(const uint8_t *p, int64_t n, int64_t limit, int32_t n_ref, int64_t first_record, uint8_t *out, int64_t cap,
+                                    int64_t *end)
 {
     kvq_clear_error();
-    if (!inflated || n < 0 || first_record < 0 || first_record > n) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_bam_to_fastq_host: bad arguments"); return -2; }
+    if (!p || n < 0 || limit < n || first_record < 0 || first_record > n) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_bam_run_host: bad arguments"); return -2; }
     kvq_bam_report rep = kvq_bam_report();
     int64_t o = first_record, t = 0;
     while (o < n) {
         KvqBamRec r;
-        if (kvq_bam_check(inflated, n, n, n_ref, o, &r) != KVQ_BAM_OK) {
-            if (consumed) *consumed = o;
+        const int v = kvq_bam_check(p, n, limit, n_ref, o, &r);
+        if (v == KVQ_BAM_BAD) {
+            if (end) *end = o;
             kvq_set_error(KVQ_ERR_IO, "malformed BAM record : offset=%ld", (long)o);
             return -1;
         }
+        if (v == KVQ_BAM_SHORT) break;                                // the record the prefix ends inside
         const int64_t len = kvq_bam_out_len(r);
         rep.records_seen++;
-        if (len) { rep.records_written++; rep.records_noqual += kvq_bam_noqual(inflated, r) ? 1 : 0; } else rep.records_skipped++;
-        if (out && t + len <= cap) for (int64_t j = 0; j < len; j++) out[t + j] = kvq_bam_char(inflated, r, j);
+        if (len) { rep.records_written++; rep.records_noqual += kvq_bam_noqual(p, r) ? 1 : 0; } else rep.records_skipped++;
+        if (out && t + len <= cap) for (int64_t j = 0; j < len; j++) out[t + j] = kvq_bam_char(p, r, j);
         t += len; o = r.next;
     }
-    if (consumed) *consumed = o;
+    if (end) *end = o;
     rep.bam_bytes = n; rep.text_bytes = t;
     g_bam_report = rep;
     return t;
 }
 
-extern "C" int64_t kvq_bam_to_fastq_device(const void *d_in, int64_t n, int32_t n_ref, int64_t first_record, void *d_out, int64_t cap,
-                                           int64_t segment_bytes, kvq_bam_report *rep_out)
+extern "C" int64_t kvq_bam_to_fastq_host(const uint8_t *inflated, int64_t n, int32_t n_ref, int64_t first_record, uint8_t *out, int64_t cap,
+                                         int64_t *consumed)
+{
+    if (!inflated || n < 0 || first_record < 0 || first_record > n) { kvq_clear_error(); kvq_set_error(KVQ_ERR_RUNTIME, "kvq_bam_to_fastq_host: bad arguments"); return -2; }
+    return kvq_bam_run_host(inflated, n, n, n_ref, first_record, out, cap, consumed);
+}
+
+extern "C" int64_t kvq_bam_run_device(const void *d_p, int64_t n, int64_t limit, int32_t n_ref, int64_t first_record, void *d_out, int64_t out_off,
+                                      int64_t cap, int64_t segment_bytes, int64_t *end, kvq_bam_report *rep_out)
 {
     kvq_clear_error();
-    if (!d_in || n < 0 || first_record < 0 || first_record > n || cap < 0 || segment_bytes < 0 || segment_bytes > (64 << 20)) {
-        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_bam_to_fastq_device: bad arguments"); return -2;
+    if (!d_p || n < 0 || limit < n || first_record < 0 || first_record > n || out_off < 0 || cap < 0 || segment_bytes < 0 || segment_bytes > (64 << 20)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_bam_run_device: bad arguments"); return -2;
     }
     const int64_t sb = segment_bytes > 0 ? segment_bytes : bam_segment_bytes_default();
     kvq_bam_report rep = kvq_bam_report();
     BamRunOut ro;
-    int rc = bam_run_find((const uint8_t *)d_in, n, n, n_ref, first_record, sb, 0, rep, ro);
+    int rc = bam_run_find((const uint8_t *)d_p, n, limit, n_ref, first_record, sb, 0, rep, ro);
     if (rc) return -2;
     rep.runs = 1;
+    if (end) *end = ro.end;
     if (ro.err >= 0) {
         g_bam_report = rep; if (rep_out) *rep_out = rep;
         kvq_set_error(KVQ_ERR_IO, "malformed BAM record : offset=%ld", (long)ro.err);
         return -1;
     }
-    if (d_out && ro.text <= cap) {
+    if (d_out && out_off + ro.text <= cap) {
         const double t0 = now_ms();
-        if (bam_run_emit((const uint8_t *)d_in, first_record, sb, ro, (uint8_t *)d_out, 0, cap, 0)) return -2;
+        if (bam_run_emit((const uint8_t *)d_p, first_record, sb, ro, (uint8_t *)d_out, out_off, cap, 0)) return -2;
         if (hipStreamSynchronize(0) != hipSuccess) { (void)hipGetLastError(); kvq_set_error(KVQ_ERR_DEVICE, "device failure in kvq_bam_emit"); return -2; }
         rep.ms_emit += now_ms() - t0;
     }
     rep.bam_bytes = n; rep.text_bytes = ro.text;
     g_bam_report = rep; if (rep_out) *rep_out = rep;
     return ro.text;
+}
+
+extern "C" int64_t kvq_bam_to_fastq_device(const void *d_in, int64_t n, int32_t n_ref, int64_t first_record, void *d_out, int64_t cap,
+                                           int64_t segment_bytes, kvq_bam_report *rep_out)
+{
+    if (!d_in || n < 0 || first_record < 0 || first_record > n || cap < 0 || segment_bytes < 0 || segment_bytes > (64 << 20)) {
+        kvq_clear_error(); kvq_set_error(KVQ_ERR_RUNTIME, "kvq_bam_to_fastq_device: bad arguments"); return -2;
+    }
+    return kvq_bam_run_device(d_in, n, n, n_ref, first_record, d_out, 0, cap, segment_bytes, nullptr, rep_out);
 }
