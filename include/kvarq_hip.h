@@ -418,6 +418,40 @@ const int64_t *kvq_scan_adapters(const kvq_scan *s);
 int32_t        kvq_adapt_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
                               const uint8_t *const *probes, const int32_t *lens, int32_t n, int64_t *out);
 
+/* ---- adapter clipping: THE SCORES OF AN ADAPTER BECOME PHRED 0 AHEAD OF THE TRIM ----
+ * The trim takes the longest run of score bytes >= Amin, compared as signed chars (workhorse.c:1055-1068).  With the score bytes
+ * from the adapter's first base on set to '!' before the scan, no trimmed read reaches into the adapter, whichever kernel trims it.
+ * MASK(text, chunk_off, probes): the record set is the profile's (every complete four-newline record of every chunk, newlines at
+ * n0 < n1 < n2 < n3).  Per record: L and CLIP are those of the adapter content above, word for word (the bases line without a
+ * trailing '\r'; FIRST_k, TAIL_k with T = 6; CLIP the minimum of those and L).  S is the length of the score line -- the bytes
+ * strictly between n2 and n3 -- less a trailing '\r'.  A record is CLIPPED when CLIP < L; then every byte text[n2 + 1 + p] with
+ * CLIP <= p < S becomes '!' (0x21).  Nothing else changes: not a '\r', a newline, the bases line, an unclipped record or a score
+ * line no longer than CLIP.  MASK is idempotent: the bases decide, and the bases do not change.
+ * THE RESULT: one flat int64 array of kvq_clip_len() = 8 words, every word but [0] a sum over the records:
+ *   [0] n     [1] records     [2] clipped records     [3] sum of max(0, S - CLIP) over the clipped records (positions, not
+ *   changes: the same on a text that is already masked)     [4] sum of L - CLIP     [5..7] 0
+ * THE CONTRACT: for every route and option the scan of `text` with the clip on returns what the same scan without it returns on
+ * MASK(text): hits, hit bytes, stats, counters, coverage, mutations, the records of the hits (their score lines carry the '!')
+ * and every word of the profile; the adapter content is that of the unmasked text, the bases being the same.
+ * THE MASK IS WRITTEN INTO THE BATCH WHERE IT LIES: the library's staging buffer of a host batch, its own buffer on the
+ * device-inflate, gzip and BAM routes, and THE CALLER'S BUFFER for kvq_scan_device -- with the clip on, that buffer is written.
+ * A batch that runs again (the redo of a batch whose speculation failed, a rescan after an arena overflow, a device batch named
+ * again) is masked again, which changes nothing; the eight words are cleared wherever the hit arena is and counted anew.
+ * kvq_scan_set_clip: n probes (rules as for kvq_scan_set_adapters) turn the clip on, n == 0 turns it off; before the first batch
+ * or after kvq_scan_reset, as kvq_scan_set_cycles.  It needs no profile and is allowed with a communicator (the words are then
+ * the rank's own).  KVQ_ERR_RUNTIME for probes outside the rules and for a table whose Amin, as a signed char, is <= '!': there
+ * '!' ends no run and a mask cannot clip.  kvq_scan_clip: the array (valid after kvq_scan_finish until the next reset), NULL
+ * when the option is off.  Off, nothing is enqueued or allocated. */
+enum { KVQ_CLIP_N = 0, KVQ_CLIP_RECORDS = 1, KVQ_CLIP_CLIPPED = 2, KVQ_CLIP_MASKED = 3, KVQ_CLIP_BASES_CUT = 4, KVQ_CLIP_WORDS = 8 };
+int64_t        kvq_clip_len(void);
+int32_t        kvq_scan_set_clip(kvq_scan *s, const uint8_t *const *probes, const int32_t *lens, int32_t n);
+const int64_t *kvq_scan_clip(const kvq_scan *s);
+/* host only, plain C++: the CPU twin of kvq_clip_records over the same definition -- test infrastructure and the definition in
+ * running code, not a fallback.  Arguments as for kvq_adapt_host, but the text is WRITTEN: masked in place.  ADDS into
+ * out[0, kvq_clip_len()), but for [0], which it sets. */
+int32_t        kvq_clip_host(uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                             const uint8_t *const *probes, const int32_t *lens, int32_t n, int64_t *out);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -428,6 +462,7 @@ double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_prof
 double  kvq_scan_reads_kernel_ms(const kvq_scan *s);     /* ... and for kvq_reads_records and the table's settle kernels (0 when both are off) */
 double  kvq_scan_over_kernel_ms(const kvq_scan *s);      /* ... and for kvq_over_records alone (0 when the overrepresented sequences are off) */
 double  kvq_scan_adapt_kernel_ms(const kvq_scan *s);     /* ... and for kvq_adapt_records alone (0 when the adapters are off) */
+double  kvq_scan_clip_kernel_ms(const kvq_scan *s);      /* ... and for kvq_clip_records alone (0 when the clip is off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 /* (measurement) how kvq_scan_finish put the hits of the finished scan in order:
@@ -595,6 +630,10 @@ typedef struct kvq_find_opts_adapters {
     uint8_t  lens[8];
     uint8_t  probes[8][32];
 } kvq_find_opts_adapters;
+/* KVQ_FIND_CLIP: kvq_scan_set_clip for the call (kvq_scan_clip after it), with the probes of kvq_find_opts_adapters -- the one
+ * probe block there is: with KVQ_FIND_ADAPTERS too, both take the same probes.  Refused ("bad size") when base.size does not
+ * cover that structure.  It is not tied to KVQ_FIND_PROFILE. */
+#define KVQ_FIND_CLIP 2048u
 kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
                             const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts);
 

@@ -19,6 +19,7 @@ FIND_CYCLES = 16                                                 # ... and count
 FIND_READ_STATS, FIND_DUPLICATION = 128, 256                     # ... the per-read distributions, the duplication (with FIND_PROFILE)
 FIND_OVERREPRESENTED = 512                                       # ... the overrepresented sequences (with FIND_PROFILE)
 FIND_ADAPTERS = 1024                                             # ... the adapter content (with FIND_PROFILE; the probes in FindOptsAdapters)
+FIND_CLIP = 2048                                                 # ... the adapter clip ahead of the trim (no profile needed; the same probe block)
 READ_STATS, READ_DUPLICATION = 1, 2                            # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
@@ -149,6 +150,11 @@ PROTOTYPES = {
     'kvq_scan_adapters': (P(i64), [vp]),
     'kvq_adapt_host': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, P(i64)]),
     'kvq_scan_adapt_kernel_ms': (C.c_double, [vp]),
+    'kvq_clip_len': (i64, []),
+    'kvq_scan_set_clip': (i32, [vp, P(cp), P(i32), i32]),
+    'kvq_scan_clip': (P(i64), [vp]),
+    'kvq_clip_host': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, P(i64)]),
+    'kvq_scan_clip_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

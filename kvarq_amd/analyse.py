@@ -46,6 +46,7 @@ class Analyser(object):
         self.hits = self.hitseqs = self.stats = self.config = None
         self.records = None                     # the FastQ record of every hit, when ``scan`` kept them (records=True)
         self.profile = None                     # the profile of the input, when ``scan`` took one (profile=<cutoffs>)
+        self.clip = None                        # what the adapter clip did, when ``scan`` clipped (clip=<probes>): a ``profile.Clip``
         self.results = {}                       # testsuite interpretation is out of scope: stays empty
         self.scantime = -1
 
@@ -72,7 +73,8 @@ class Analyser(object):
         ``self.profile`` (``encode`` then adds ``info['profile']``); ``cycles=True`` takes the per-cycle counts into it
         (``info['profile']['cycles']``), ``per_read=True`` / ``duplication=True`` the per-read distributions / the
         duplication (``info['profile']['per_read']`` / ``['duplication']``), ``overrepresented=True`` the overrepresented
-        sequences (``info['profile']['overrepresented']``), ``adapters=`` the adapter content (``info['profile']['adapters']``); ``long_reads``: as for ``engine.findseqs``,
+        sequences (``info['profile']['overrepresented']``), ``adapters=`` the adapter content (``info['profile']['adapters']``); ``clip=`` masks the
+        scores of adapters ahead of the trim and keeps what it did in ``self.clip``; ``long_reads``: as for ``engine.findseqs``,
         which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
@@ -90,6 +92,7 @@ class Analyser(object):
         self.stats, self.hits, self.hitseqs = ret['stats'], ret['hits'], ret['hitseqs']
         self.records = ret.get('records')
         self.profile = ret.get('profile')
+        self.clip = ret.get('clip')
         self.scantime = time.time() - t0
         self.update_coverages()
 

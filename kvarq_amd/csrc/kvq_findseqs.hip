@@ -189,17 +189,18 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_OVERREPRESENTED needs KVQ_FIND_PROFILE (the overrepresented sequences ride on the profile)");
         return nullptr;
     }
-    // the probes of KVQ_FIND_ADAPTERS ride behind the 20 bytes of kvq_find_opts: read only with the flag, and only when the size covers them
+    // the probes of KVQ_FIND_ADAPTERS and KVQ_FIND_CLIP -- one block for both -- ride behind the 20 bytes of kvq_find_opts: read only with
+    // one of the flags, and only when the size covers them
     const uint8_t *probes[KVQ_ADAPT_MAX_PROBES] = { nullptr }; int32_t probe_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }, nprobes = 0;
-    if (flags & KVQ_FIND_ADAPTERS) {
-        if (!(flags & KVQ_FIND_PROFILE)) {
-            kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTERS needs KVQ_FIND_PROFILE (the adapter content rides on the profile)");
-            return nullptr;
-        }
+    if ((flags & KVQ_FIND_ADAPTERS) && !(flags & KVQ_FIND_PROFILE)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTERS needs KVQ_FIND_PROFILE (the adapter content rides on the profile)");
+        return nullptr;
+    }
+    if (flags & (KVQ_FIND_ADAPTERS | KVQ_FIND_CLIP)) {
         const kvq_find_opts_adapters *oa = (const kvq_find_opts_adapters *)opts;
         if (!opts || opts->size < sizeof(kvq_find_opts_adapters)) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: bad size"); return nullptr; }
         if (oa->n_probes < 1 || oa->n_probes > KVQ_ADAPT_MAX_PROBES) {
-            kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTERS takes 1 to %d probes", KVQ_ADAPT_MAX_PROBES);
+            kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTERS and KVQ_FIND_CLIP take 1 to %d probes", KVQ_ADAPT_MAX_PROBES);
             return nullptr;
         }
         nprobes = oa->n_probes;
@@ -243,7 +244,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
               kvq_scan_set_cycles(s, (flags & KVQ_FIND_CYCLES) ? 1 : 0) ||
               kvq_scan_set_read_stats(s, ((flags & KVQ_FIND_READ_STATS) ? KVQ_READ_STATS : 0) | ((flags & KVQ_FIND_DUPLICATION) ? KVQ_READ_DUPLICATION : 0)) ||
               kvq_scan_set_overrepresented(s, (flags & KVQ_FIND_OVERREPRESENTED) ? 1 : 0) ||
-              kvq_scan_set_adapters(s, probes, probe_lens, nprobes))) {
+              kvq_scan_set_adapters(s, probes, probe_lens, (flags & KVQ_FIND_ADAPTERS) ? nprobes : 0) ||
+              kvq_scan_set_clip(s, probes, probe_lens, (flags & KVQ_FIND_CLIP) ? nprobes : 0))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
     }
     const double tf1 = now_ms();
@@ -322,7 +324,7 @@ extern "C" kvq_scan *kvq_findseqs_ex(const char *const *files, int32_t nfiles,
     kvq_find_opts o; memset(&o, 0, sizeof(o));
     o.size = (uint32_t)sizeof(o); o.flags = flags & ~(KVQ_FIND_PROFILE | KVQ_FIND_CYCLES);       // (the profile has cutoffs: kvq_findseqs_opts)
     // (... but for the per-read statistics, which need none: with them KVQ_FIND_PROFILE is a profile with no cutoffs)
-    // (KVQ_FIND_ADAPTERS goes through as it is: this structure has no room for probes, and the flag without them is "bad size")
+    // (KVQ_FIND_ADAPTERS and KVQ_FIND_CLIP go through as they are: this structure has no room for probes, and the flags without them are "bad size")
     if ((flags & (KVQ_FIND_READ_STATS | KVQ_FIND_DUPLICATION | KVQ_FIND_OVERREPRESENTED | KVQ_FIND_ADAPTERS)) && (flags & KVQ_FIND_PROFILE)) o.flags = flags;
     return kvq_findseqs_opts(files, nfiles, seqs, seqlens, nseq, &o);
 }

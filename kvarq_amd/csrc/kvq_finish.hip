@@ -406,6 +406,7 @@ extern "C" double kvq_scan_cycles_kernel_ms(const kvq_scan *s) { return s->passe
 extern "C" double kvq_scan_reads_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_READS].ms; }
 extern "C" double kvq_scan_over_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_OVER].ms; }
 extern "C" double kvq_scan_adapt_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_ADAPT].ms; }
+extern "C" double kvq_scan_clip_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_CLIP].ms; }
 // (measurement) ms from the end of a's last main kernel to the start of b's first one (both finished, neither reset since); < 0: unknown
 extern "C" double kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b)
 {

@@ -142,7 +142,8 @@ int kvq_comm_max_status(kvq_comm *c, unsigned long long mine, unsigned long long
 
 // An input pass: a kernel that every batch runs once over its exact record index and that adds to one device array, which the
 // tail of the scan brings to the host.  The cycles' array has the kernel's own scratch word behind the words that land.
-enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASS_ADAPT, KVQ_PASSES };
+// (the clip is no pass behind the scan: its kernel runs in front of it and needs no profile -- clip_text in kvq_scan.hip; its array shares the lifecycle)
+enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASS_ADAPT, KVQ_PASS_CLIP, KVQ_PASSES };
 typedef std::pair<hipEvent_t, hipEvent_t> KvqEventPair;
 struct KvqPass {
     bool on = false;
@@ -247,6 +248,8 @@ struct kvq_scan {
     uint64_t over_M = 0, over_slots = 0, over_seen = 0;
     // the adapter content: the probes (kvq_scan_set_adapters; adapt_n == 0: off)
     int32_t adapt_n = 0; uint8_t adapt_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t adapt_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
+    // the adapter clip (kvq_scan_set_clip): its probes (clip_n == 0: off); its array is passes[KVQ_PASS_CLIP]
+    int32_t clip_n = 0; uint8_t clip_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t clip_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
 };
 
 // kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal

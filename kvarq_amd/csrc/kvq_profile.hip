@@ -1,5 +1,5 @@
 // kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16, 17 and 18), host side: the profile, the
-// per-cycle counts, the per-read statistics, the overrepresented sequences and the adapter content as options of a scan object, the steps of their common lifecycle, the launch of
+// per-cycle counts, the per-read statistics, the overrepresented sequences, the adapter content and the adapter clip (section 19) as options of a scan object, the steps of their common lifecycle, the launch of
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
 #include <array>
@@ -146,6 +146,7 @@ static void passes_landed(kvq_scan *s)
         h[KVQ_ADAPT_N] = s->adapt_n;
         for (int k = 0; k < s->adapt_n; k++) h[KVQ_ADAPT_BLOCKS + (size_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = s->adapt_lens[k];
     }
+    if (s->passes[KVQ_PASS_CLIP].on) s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_N] = s->clip_n;      // (the word that is no sum)
 }
 // what an accessor hands out: the copy of a pass that is on, of a finished scan
 static const int64_t *pass_result(const kvq_scan *s, int which)
@@ -381,18 +382,25 @@ extern "C" int32_t kvq_scan_set_adapters(kvq_scan *s, const uint8_t *const *prob
     return pass_clear(s, KVQ_PASS_ADAPT);
 }
 
+// n probes as the kernels take them, by value: 2-bit codes, masks and lengths (kvq_adapt_records and kvq_clip_records)
+static KvqAdaptProbes adapt_probes(int32_t n, const uint8_t *lens, const uint8_t (*probes)[KVQ_ADAPT_MAX_PROBE])
+{
+    KvqAdaptProbes P; memset(&P, 0, sizeof(P));
+    P.n = (uint32_t)n;
+    for (int k = 0; k < n; k++) {
+        const uint32_t m = lens[k];
+        for (uint32_t i = 0; i < m; i++) P.code[k] |= (unsigned long long)((probes[k][i] >> 1) & 3u) << (2u * i);
+        P.mask[k] = m >= 32u ? ~0ull : (1ull << (2u * m)) - 1ull;               // (no shift by 64)
+        P.m[k] = m;
+    }
+    return P;
+}
+
 // the pass over the R records of a batch, behind its other passes: the probes go along by value, as 2-bit codes
 static int adapt_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
 {
     if (R == 0) return KVQ_OK;
-    KvqAdaptProbes P; memset(&P, 0, sizeof(P));
-    P.n = (uint32_t)s->adapt_n;
-    for (int k = 0; k < s->adapt_n; k++) {
-        const uint32_t m = s->adapt_lens[k];
-        for (uint32_t i = 0; i < m; i++) P.code[k] |= (unsigned long long)((s->adapt_probes[k][i] >> 1) & 3u) << (2u * i);
-        P.mask[k] = m >= 32u ? ~0ull : (1ull << (2u * m)) - 1ull;               // (no shift by 64)
-        P.m[k] = m;
-    }
+    const KvqAdaptProbes P = adapt_probes(s->adapt_n, s->adapt_lens, s->adapt_probes);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
     hipLaunchKernelGGL(kvq_adapt_kernel(P.n), dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
                        (uint32_t)R, P, s->passes[KVQ_PASS_ADAPT].d.as<unsigned long long>());
@@ -401,3 +409,46 @@ static int adapt_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
 }
 
 extern "C" const int64_t *kvq_scan_adapters(const kvq_scan *s) { return pass_result(s, KVQ_PASS_ADAPT); }
+
+// ---- adapter clipping ----
+// Its array goes through the lifecycle above (made, cleared, landed and given back as the others'), but the clip is no pass behind
+// a batch's scan: its kernel runs in front of it (clip_text in kvq_scan.hip), and it needs no profile.
+extern "C" int64_t kvq_clip_len(void) { return KVQ_CLIP_WORDS; }
+
+static void clip_off(kvq_scan *s)
+{
+    s->clip_n = 0;
+    pass_off(s, s->passes[KVQ_PASS_CLIP]);
+}
+
+extern "C" int32_t kvq_scan_set_clip(kvq_scan *s, const uint8_t *const *probes, const int32_t *lens, int32_t n)
+{
+    int rc;
+    kvq_clear_error();
+    if ((rc = scan_idle(s, "kvq_scan_set_clip"))) return rc;
+    if (n == 0) { clip_off(s); return KVQ_OK; }
+    if (!adapt_probes_ok("kvq_scan_set_clip", probes, lens, n)) return KVQ_ERR_RUNTIME;
+    if ((int)(int8_t)s->t->cfg.Amin <= (int)'!') {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_clip: Amin %d is not above '!' (33): a masked score would end no run, and the mask could not clip", (int)(int8_t)s->t->cfg.Amin);
+        return KVQ_ERR_RUNTIME;
+    }
+    if ((rc = pass_make(s->passes[KVQ_PASS_CLIP], (size_t)KVQ_CLIP_WORDS * 8, KVQ_CLIP_WORDS, (size_t)KVQ_CLIP_WORDS * 8))) { clip_off(s); return rc; }
+    s->clip_n = n;
+    memset(s->clip_lens, 0, sizeof(s->clip_lens)); memset(s->clip_probes, 0, sizeof(s->clip_probes));
+    for (int32_t k = 0; k < n; k++) { s->clip_lens[k] = (uint8_t)lens[k]; memcpy(s->clip_probes[k], probes[k], (size_t)lens[k]); }
+    return pass_clear(s, KVQ_PASS_CLIP);
+}
+
+// the clip over the R records of a batch whose index is on the scan's stream, in front of its scan: the text at d_data is written
+static int clip_enqueue(kvq_scan *s, uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    const KvqAdaptProbes P = adapt_probes(s->clip_n, s->clip_lens, s->clip_probes);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
+    hipLaunchKernelGGL(kvq_clip_kernel(P.n), dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, P,
+                       s->passes[KVQ_PASS_CLIP].d.as<unsigned long long>());
+    KVQ_HIP(hipGetLastError());
+    return KVQ_OK;
+}
+
+extern "C" const int64_t *kvq_scan_clip(const kvq_scan *s) { return pass_result(s, KVQ_PASS_CLIP); }

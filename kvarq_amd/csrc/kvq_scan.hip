@@ -406,6 +406,26 @@ static int index_records(kvq_scan *s, BatchRun &B)
     return KVQ_OK;
 }
 
+// The adapter clip (kvq_scan_set_clip), in front of everything that reads the batch's scores: the exact index --
+// which the exhaustive pass and the profile then take as it is --, and kvq_clip_records over it, which WRITES the batch's text
+// where it lies.  Every first run of a batch, a replay after an arena overflow among them (the array has been cleared with the
+// arena: the records are counted anew, and masking a masked text changes nothing); the exhaustive redo of a failed batch leaves it
+// alone -- its text is masked and its records are counted.
+static int clip_text(kvq_scan *s, BatchRun &B)
+{
+    int rc;
+    // (a seed-filter batch copies its chunk offsets together with its tables, behind this step: the index wants them now)
+    if (B.use_seeded) KVQ_HIP(hipMemcpyAsync(s->pool.d + s->cur_co_at, s->pool.h + s->cur_co_at, ((size_t)B.nchunks + 1) * 4, hipMemcpyHostToDevice, s->stream));
+    if ((rc = index_records(s, B))) return rc;
+    KvqPass &p = s->passes[KVQ_PASS_CLIP];
+    if (B.nrec <= 0) return KVQ_OK;
+    if ((rc = new_event_pair(s, p.ev))) return rc;
+    KVQ_HIP(hipEventRecord(p.ev.back().first, s->stream));
+    if ((rc = clip_enqueue(s, const_cast<uint8_t *>(B.d_data), (uint64_t)B.nrec))) return rc;
+    KVQ_HIP(hipEventRecord(p.ev.back().second, s->stream));
+    return KVQ_OK;
+}
+
 // The exhaustive pass over every record of the batch, for the n_exh sequences of d_exh (none: only the records are counted,
 // when no seed-filter launch has done it).
 static int exhaustive_pass(kvq_scan *s, BatchRun &B, const int32_t *d_exh, int32_t n_exh, bool hist_done)
@@ -413,7 +433,7 @@ static int exhaustive_pass(kvq_scan *s, BatchRun &B, const int32_t *d_exh, int32
     int rc;
     const uint8_t *d_data = B.d_data;
     if (n_exh > 0) s->path_bits |= 2;
-    if ((rc = index_records(s, B))) return rc;
+    if (B.nrec < 0 && (rc = index_records(s, B))) return rc;      // (clip_text has made the index of a batch it masked)
     const uint64_t R = (uint64_t)B.nrec;
     if (R == 0) return KVQ_OK;
     if ((rc = s->d_read_off.ensure((size_t)R * 4)) || (rc = s->d_read_len.ensure((size_t)R * 4))) return rc;
@@ -531,6 +551,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
     if ((rc = chunk_table(s, B, b.chunk_off.data()))) return rc;
     if ((rc = new_event_pair(s, s->ev_all))) return rc;
     KVQ_HIP(hipEventRecord(s->ev_all.back().first, s->stream));
+    if (s->clip_n && !exhaustive_only && (rc = clip_text(s, B))) return rc;
 
     if (B.use_seeded) {
         if ((rc = new_event_pair(s, s->ev_main))) return rc;
@@ -566,7 +587,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
         if (B.nrec < 0 && (rc = index_records(s, B))) return rc;
         for (int i = 0; i < KVQ_PASSES && B.nrec > 0; i++) {
             KvqPass &p = s->passes[i];
-            if (!p.on) continue;
+            if (!p.on || i == KVQ_PASS_CLIP) continue;     // (the clip has run in front of the scan: clip_text)
             if ((rc = new_event_pair(s, p.ev))) return rc;
             KVQ_HIP(hipEventRecord(p.ev.back().first, s->stream));
             switch (i) {

@@ -1,7 +1,7 @@
-// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16, 17 and 18): the
-// definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records, kvq_over_records and kvq_adapt_records in plain C++
-// (test infrastructure, never a fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record
-// walk serve all five.
+// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes and of the adapter clip (include/kvarq_hip.h, DESIGN sections 13,
+// 14, 16, 17, 18 and 19): the definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records, kvq_over_records,
+// kvq_adapt_records and kvq_clip_records in plain C++ (test infrastructure, never a fallback).  Nothing of HIP: the file also
+// compiles on its own.  One argument check and one record walk serve all six.
 #include "../../include/kvarq_hip.h"
 #include "kvq_dup_hash.h"
 #include <algorithm>
@@ -204,6 +204,35 @@ extern "C" int32_t kvq_adapt_host(const uint8_t *text, int64_t nbytes, const int
         out[KVQ_ADAPT_RECORDS]++;
         out[full ? KVQ_ADAPT_WITH_FULL : KVQ_ADAPT_TAIL_ONLY] += full || tailed;
         out[KVQ_ADAPT_CLIP + std::min<int64_t>(clip, KVQ_ADAPT_CLIP_BINS - 1)]++;
+    });
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_clip_host(uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                 const uint8_t *const *probes, const int32_t *lens, int32_t n, int64_t *out)
+{
+    if (!twin_args("kvq_clip_host", out != nullptr, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    if (!adapt_probes_ok("kvq_clip_host", probes, lens, n)) return KVQ_ERR_RUNTIME;
+    out[KVQ_CLIP_N] = n;
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
+        const uint8_t *line = text + n0 + 1;
+        int64_t L = n1 - n0 - 1, S = n3 - n2 - 1;
+        if (L > 0 && line[L - 1] == '\r') L--;                                 // a trailing '\r' is not part of its line
+        if (S > 0 && text[n2 + S] == '\r') S--;
+        int64_t clip = L;
+        for (int32_t k = 0; k < n; k++) {
+            const int64_t m = lens[k];
+            int64_t first = -1, tail = -1;
+            for (int64_t p = 0; first < 0 && p + m <= L; p++) if (!memcmp(line + p, probes[k], (size_t)m)) first = p;
+            for (int64_t t = std::min(m - 1, L); first < 0 && tail < 0 && t >= KVQ_ADAPT_MIN_TAIL; t--)
+                if (!memcmp(line + L - t, probes[k], (size_t)t)) tail = t;
+            if (first >= 0) clip = std::min(clip, first);
+            else if (tail >= 0) clip = std::min(clip, L - tail);
+        }
+        out[KVQ_CLIP_RECORDS]++;
+        if (clip >= L) return;
+        out[KVQ_CLIP_CLIPPED]++; out[KVQ_CLIP_MASKED] += std::max<int64_t>(0, S - clip); out[KVQ_CLIP_BASES_CUT] += L - clip;
+        for (int64_t p = clip; p < S; p++) text[n2 + 1 + p] = '!';
     });
     return KVQ_OK;
 }

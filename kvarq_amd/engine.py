@@ -215,6 +215,13 @@ def findseqs(fname, sequences, *, inflate='host', **options):
     of ``profile.KNOWN_SOURCES`` that are bytes.  1 to 8 probes of 8 to 32 upper-case A C G T, matched
     byte for byte.  Without ``profile`` it means a profile with no cutoffs.
 
+    clip=True / {name: bytes} / [bytes, ...] (the forms of ``adapters``; with both, the same probes): adapter
+    clipping ahead of the trim.  The score bytes of every record from its adapter's first
+    base on -- the ``CLIP`` of the adapter content -- are set to '!' (Phred 0) on the GPU before the batch is
+    scanned, so no trimmed read reaches into the adapter: the results are those of a scan of the masked
+    text.  The dict gains 'clip' (``profile.Clip``: ``records``, ``clipped``, ``masked``, ``bases_cut``,
+    ``words``) and 'clip_kernel_ms'.  It needs no profile; a configured Amin of '!' or below is refused.
+
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
     no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are
@@ -290,6 +297,10 @@ def findseqs(fname, sequences, *, inflate='host', **options):
         if opt.profile is not None:
             from . import profile as profile_
             out['profile'] = profile_.from_scan(L, h, adapters=(opt.adapter_names, opt.adapters))
+        if opt.clip:
+            from . import profile as profile_
+            out['clip'] = profile_.clip_from_scan(L, h, (opt.clip_names, opt.clip))
+            out['clip_kernel_ms'] = L.kvq_scan_clip_kernel_ms(h)
         return out
     finally:
         if h:

@@ -1,6 +1,6 @@
 """
 The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
-``duplication``, ``overrepresented``, ``adapters`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+``duplication``, ``overrepresented``, ``adapters``, ``clip`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
 everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
 """
 import ctypes as C
@@ -15,10 +15,13 @@ class ScanOptions(object):
     ``duplication``; ``overrepresented``: the overrepresented sequences; ``long_mode``: the mode of kvq_scan_set_long_reads
     for ``long_reads`` (False, True or 'auto'); ``adapters``: the probes of the adapter content (``profile.as_adapters``: True,
     a mapping name -> bytes or a list of bytes; None or False: off) -- ``adapter_names`` and ``adapters``, a list of bytes, here.
-    ``cycles``, ``per_read``, ``duplication``, ``overrepresented`` or ``adapters`` without ``profile`` mean a profile with no cutoffs."""
+    ``cycles``, ``per_read``, ``duplication``, ``overrepresented`` or ``adapters`` without ``profile`` mean a profile with no cutoffs.
+    ``clip``: the probes of the adapter clip ahead of the trim, in the forms of ``adapters`` -- ``clip_names`` and
+    ``clip``, a list of bytes, here; it needs no profile.  ``adapters`` and ``clip`` together must name the same probes (``findseqs``
+    has one probe block): otherwise ValueError."""
 
     def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, overrepresented=False,
-                 adapters=None, amin=None):
+                 adapters=None, clip=None, amin=None):
         self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
         self.records, self.cycles, self.overrepresented = bool(records), bool(cycles), bool(overrepresented)
         self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
@@ -26,6 +29,16 @@ class ScanOptions(object):
         if adapters is not None and adapters is not False:
             from .profile import as_adapters
             self.adapter_names, self.adapters = as_adapters(adapters)
+        self.clip_names, self.clip = None, None
+        if clip is not None and clip is not False:
+            from .profile import as_adapters
+            self.clip_names, self.clip = as_adapters(clip)
+            if self.adapters and self.adapters != self.clip:
+                raise ValueError('adapters= and clip= must name the same probes')
+            # (where the caller knows the table's Amin: what kvq_scan_set_clip refuses, refused before a scan object is made)
+            a = None if amin is None else amin & 0xFF if isinstance(amin, int) else (amin.encode('latin-1') if isinstance(amin, str) else bytes(amin))[0]
+            if a is not None and (a ^ 0x80) - 0x80 <= ord('!'):
+                raise ValueError("clip= needs an Amin above '!': a masked score would end no run")
         if (self.cycles or self.read_stats or self.overrepresented or self.adapters) and profile is None:
             profile = ()
         self.profile = None
@@ -41,12 +54,13 @@ class ScanOptions(object):
                       (_lib.FIND_DUPLICATION if self.read_stats & _lib.READ_DUPLICATION else 0) | (_lib.FIND_OVERREPRESENTED if self.overrepresented else 0))
         cuts = self.profile or ()
         base = _lib.FindOpts(C.sizeof(_lib.FindOpts), flags, len(cuts), (C.c_uint8 * 8)(*cuts))
-        if not self.adapters:
+        probes = self.adapters or self.clip
+        if not probes:
             return base
-        # (the probes ride behind the 20 bytes, which stay what they are whenever the adapters are off)
-        base.size, base.flags = C.sizeof(_lib.FindOptsAdapters), flags | _lib.FIND_ADAPTERS
-        o = _lib.FindOptsAdapters(base, len(self.adapters), (C.c_uint8 * 8)(*[len(p) for p in self.adapters]))
-        for k, p in enumerate(self.adapters):
+        # (the probes ride behind the 20 bytes, which stay what they are whenever the adapters and the clip are off)
+        base.size, base.flags = C.sizeof(_lib.FindOptsAdapters), flags | (_lib.FIND_ADAPTERS if self.adapters else 0) | (_lib.FIND_CLIP if self.clip else 0)
+        o = _lib.FindOptsAdapters(base, len(probes), (C.c_uint8 * 8)(*[len(p) for p in probes]))
+        for k, p in enumerate(probes):
             C.memmove(o.probes[k], p, len(p))
         return o
 
@@ -64,6 +78,9 @@ class ScanOptions(object):
             if self.adapters:
                 n = len(self.adapters)
                 calls.append(('kvq_scan_set_adapters', ((C.c_char_p * n)(*self.adapters), (C.c_int32 * n)(*[len(p) for p in self.adapters]), n)))
+        if self.clip:
+            n = len(self.clip)
+            calls.append(('kvq_scan_set_clip', ((C.c_char_p * n)(*self.clip), (C.c_int32 * n)(*[len(p) for p in self.clip]), n)))
         if self.long_mode:
             calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
         return calls

@@ -265,6 +265,7 @@ class Profile(object):
     def __init__(self, words, cutoffs, cycles=None, reads=None, dup=None, over=None, sources=None, adapters=None):
         self.cutoffs = list(cutoffs)
         self.adapters = adapters
+        self.clipped = None                     # the ``Clip`` of a scan with ``clip=`` (set by ``profile`` and ``profile_host``)
         self.over = self.over_info = self.overrepresented = None
         if over is not None:
             self.over = np.array(over, dtype=np.int64)
@@ -633,6 +634,58 @@ class Profile(object):
         return d
 
 
+CLIP_N, CLIP_RECORDS, CLIP_CLIPPED, CLIP_MASKED, CLIP_BASES_CUT, CLIP_LEN = 0, 1, 2, 3, 4, 8      # (include/kvarq_hip.h: kvq_clip_len())
+
+
+class Clip(object):
+    """what the adapter clip of a scan did (kvq_scan_clip; the definition: include/kvarq_hip.h): ``records``,
+    ``clipped`` (records whose adapter begins inside the read), ``masked`` (score positions set to '!'), ``bases_cut`` (bases
+    behind the clips), ``words`` (the eight words), ``names`` and ``probes``"""
+
+    def __init__(self, words, names=None, probes=None):
+        w = self.words = np.asarray(words, dtype=np.int64)
+        assert w.shape == (CLIP_LEN,)
+        self.records, self.clipped, self.masked, self.bases_cut = int(w[CLIP_RECORDS]), int(w[CLIP_CLIPPED]), int(w[CLIP_MASKED]), int(w[CLIP_BASES_CUT])
+        self.names, self.probes = names, probes
+
+    def __eq__(self, other):
+        return isinstance(other, Clip) and np.array_equal(self.words, other.words)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __getitem__(self, key):
+        if key not in ('records', 'clipped', 'masked', 'bases_cut', 'words'):
+            raise KeyError(key)
+        return getattr(self, key)
+
+    def line(self):
+        return 'clip: records=%d clipped=%d (%.4f) masked=%d bases_cut=%d' % (
+            self.records, self.clipped, self.clipped / float(self.records) if self.records else float('nan'), self.masked, self.bases_cut)
+
+
+def clip_from_scan(L, h, clip=None):
+    """the ``Clip`` of a finished scan object, None when the option is off; ``clip``: ``(names, probes)`` of ``ScanOptions``"""
+    ptr = L.kvq_scan_clip(h)
+    names, probes = clip if clip is not None else (None, None)
+    return Clip(np.ctypeslib.as_array(ptr, shape=(CLIP_LEN,)).copy(), names, probes) if ptr else None
+
+
+def clip_host(text, clip, chunk_off=None, into=None):
+    """the CPU twin of the adapter clip (kvq_clip_host) over a text in host memory: (MASK(text) as a new uint8 array, the eight
+    words); ``into``: words to add to, as the twin does"""
+    from . import scan
+    _, probes = as_adapters(clip)
+    arr = (np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)).copy()
+    co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
+    n = len(probes)
+    words = np.zeros(CLIP_LEN, dtype=np.int64) if into is None else into
+    if _lib.lib().kvq_clip_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+                                (C.c_char_p * n)(*probes), (C.c_int32 * n)(*[len(p) for p in probes]), n, words.ctypes.data_as(C.POINTER(C.c_int64))):
+        raise RuntimeError(_lib.last_error()[1])
+    return arr, words
+
+
 def from_scan(L, h, sources=None, adapters=None):
     """the profile of a finished scan object (kvq_scan_profile), None when it keeps none; ``sources``: as for ``Profile``;
     ``adapters``: ``(names, probes)`` of the scan's adapter probes (``ScanOptions``), which the flat array does not hold"""
@@ -653,14 +706,19 @@ def from_scan(L, h, sources=None, adapters=None):
 
 
 def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False, duplication=False, slots=0, overrepresented=False,
-                 over_records=0, sources=None, adapters=None):
+                 over_records=0, sources=None, adapters=None, clip=None):
     """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host; per_read / duplication: and kvq_reads_host, with a
     table of ``slots`` slots, 0: the default; overrepresented: and kvq_over_host, with the first ``over_records`` records
-    making the candidates, 0: the default; adapters: and kvq_adapt_host, with the probes of ``as_adapters``) over a text in host memory; chunk_off None: the reader's chunk cuts"""
+    making the candidates, 0: the default; adapters: and kvq_adapt_host, with the probes of ``as_adapters``) over a text in host memory; chunk_off None: the reader's chunk cuts;
+    clip: the profile of a copy of the text that kvq_clip_host has masked with these probes (``Profile.clipped``: the ``Clip``)"""
     from . import scan
     cuts = as_cutoffs(cutoffs)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
     co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
+    clipped = None
+    if clip is not None and clip is not False:
+        arr, words = clip_host(arr, clip, co)
+        clipped = Clip(words, *as_adapters(clip))
     out = np.zeros(profile_len(len(cuts)), dtype=np.int64)
     rc = _lib.lib().kvq_profile_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)),
                                      len(co) - 1, _cut_array(cuts), len(cuts), out.ctypes.data_as(C.POINTER(C.c_int64)))
@@ -688,7 +746,9 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False,
     ada = None
     if adapters is not None and adapters is not False:
         ada = adapt_host(arr, adapters, co)
-    return Profile(out, cuts, cyc, reads, dup, over, sources, ada)
+    p = Profile(out, cuts, cyc, reads, dup, over, sources, ada)
+    p.clipped = clipped
+    return p
 
 
 def adapt_host(text, adapters, chunk_off=None):
@@ -709,10 +769,13 @@ def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     """the profile of one file or several (plain, gzip, BGZF, BAM), by a scan with no sequences; ``cycles``: with the
     per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication; ``overrepresented``:
     with the overrepresented sequences, labelled from ``sources`` (None: ``KNOWN_SOURCES``); ``adapters``: with the adapter
-    content of these probes (``as_adapters``); ``long_reads``: as for
+    content of these probes (``as_adapters``); ``clip``: of the input with the scores of its adapters masked (DESIGN section 19;
+    ``Profile.clipped``: the ``Clip``); ``long_reads``: as for
     ``engine.findseqs``, which takes the ``options``"""
     from . import engine
-    p = engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)['profile']
+    r = engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)
+    p = r['profile']
+    p.clipped = r.get('clip')
     if sources is not None and p.over is not None:
         p.relabel(sources)
     return p
@@ -731,6 +794,7 @@ def main(argv=None):
     ap.add_argument('--duplication', action='store_true', help='how often the first 64 bases of the reads repeat: level, sample size and a line per count bin')
     ap.add_argument('--overrepresented', action='store_true', help='the sequences (first 64 bases) that make up 0.1 %% of the reads and more, among those of the first 2^18 records: count, share, known source')
     ap.add_argument('--adapters', nargs='*', metavar='NAME=SEQ', help='the adapter content: how many reads hold each probe and from which cycle on, tails of 6 bases and more, the length a clip would leave; without arguments: the known adapters')
+    ap.add_argument('--clip', nargs='*', metavar='NAME=SEQ', help="the profile of the input with the scores of its adapters set to '!' ahead of the trim, and how much was clipped; without arguments: the known adapters (with --adapters: the same probes)")
     a = ap.parse_args(argv)
     more = dict(cycles=a.cycles, per_read=a.per_read, duplication=a.duplication, overrepresented=a.overrepresented)
     if a.adapters is not None:
@@ -738,6 +802,11 @@ def main(argv=None):
             if '=' not in item:
                 ap.error('--adapters takes NAME=SEQ')
         more['adapters'] = collections.OrderedDict((i.split('=', 1)[0], i.split('=', 1)[1].encode('latin-1')) for i in a.adapters) if a.adapters else True
+    if a.clip is not None:
+        for item in a.clip:
+            if '=' not in item:
+                ap.error('--clip takes NAME=SEQ')
+        more['clip'] = collections.OrderedDict((i.split('=', 1)[0], i.split('=', 1)[1].encode('latin-1')) for i in a.clip) if a.clip else True
     p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
@@ -753,6 +822,8 @@ def main(argv=None):
         print('\n'.join(p.overrepresented_lines()))
     if a.adapters is not None:
         print('\n'.join(p.adapter_lines()))
+    if a.clip is not None:
+        print(p.clipped.line())
 
 
 if __name__ == '__main__':

@@ -92,12 +92,13 @@ class Scanner(object):
 
     def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, **options):
         self.table = table
-        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters (``options.ScanOptions``), set on the
+        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters, clip (``options.ScanOptions``), set on the
         # scan handle once and kept across reset
         opt = ScanOptions(amin=bytes([table.config.Amin & 0xFF]), **options)
         self.records, self.profile, self.cycles, self.read_stats, self.long_reads = opt.records, opt.profile, opt.cycles, opt.read_stats, opt.long_reads
         self.overrepresented = opt.overrepresented
         self.adapters, self.adapter_names = opt.adapters, opt.adapter_names
+        self.clip, self.clip_names = opt.clip, opt.clip_names      # (with ``clip`` the text of a batch is WRITTEN where it lies: ``scan_device``)
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
@@ -123,6 +124,8 @@ class Scanner(object):
         _lib.lib().kvq_scan_force_exhaustive(self.h, 1 if on else 0)
 
     def scan_device(self, d_ptr, nbytes, chunk_off, fpos_base=0):
+        """a batch in the caller's device memory.  With ``clip=`` THE BUFFER IS WRITTEN: the score bytes of every record from its
+        adapter's first base on become '!' where they lie"""
         co = np.ascontiguousarray(chunk_off, dtype=np.int64)
         self._device_batches.append((d_ptr, nbytes, co, fpos_base))
         _check(_lib.lib().kvq_scan_device(self.h, d_ptr, nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1, fpos_base))
@@ -199,6 +202,10 @@ class Scanner(object):
                 out['over_kernel_ms'] = L.kvq_scan_over_kernel_ms(self.h)
             if self.adapters:
                 out['adapt_kernel_ms'] = L.kvq_scan_adapt_kernel_ms(self.h)
+        if self.clip:
+            from . import profile as profile_
+            out['clip'] = profile_.clip_from_scan(L, self.h, (self.clip_names, self.clip))
+            out['clip_kernel_ms'] = L.kvq_scan_clip_kernel_ms(self.h)
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
