@@ -211,9 +211,20 @@ def end_text():
     return b''.join(rec(planted(rng, p, P12, 0)) for p in (0, 30, 140)) + rec(planted(rng, 100, P32, 0), scores=b''), [P12, P32]
 
 
+def split_text():
+    """a probe cut in two by a record's end: a line of exactly 256 bases -- one round of the search's sixteen lanes -- ends with the
+    first h bases of P32 and the NEXT record's line begins with the rest.  A tail of h and never a full occurrence, whatever a lane
+    takes from the quarter-wave beside its own (the pairs lie in quarters 0 and 1 or 2 and 3 of one wave)"""
+    rng = np.random.RandomState(28)
+    out = []
+    for h in range(16, 32):
+        out += [rec(filler(rng, 256 - h) + P32[:h]), rec(P32[h:] + filler(rng, 40))]
+    return b''.join(out), [P12, P32]
+
+
 @functools.lru_cache(maxsize=None)
 def texts():
-    return {'every_start': every_start_text(), 'edges': edges_text(), 'cr': cr_text(), 'several': several_text(), 'tails': tails_text(),
+    return {'split': split_text(), 'every_start': every_start_text(), 'edges': edges_text(), 'cr': cr_text(), 'several': several_text(), 'tails': tails_text(),
             'aliases': aliases_text(), 'shapes': shapes_text(), 'none': none_text(), 'end': end_text()}
 
 
@@ -279,6 +290,8 @@ def check_census(name):
     elif name == 'shapes':
         assert sorted(len(p) for p in probes)[:1] == [8] and {8, 12, 31, 32} <= {len(p) for p in probes} and len(probes) == 8
         assert {k for k, _ in c['first']} == set(range(8)) and {k for k, _ in c['tail']} >= {0, 1, 2, 3}
+    elif name == 'split':
+        assert {(1, h) for h in range(16, 32)} == c['tail'] and not c['first'] and c['matched'] == 16 and 256 in c['L'] and len(c['L']) == 17
     elif name == 'end':
         assert text.endswith(b'\n+\n\n') and c['last_flush'][0][1] == 100 and 100 + 32 == sorted(c['L'])[-2]
     return c
