@@ -487,6 +487,28 @@ void    kvq_scan_order_info(const kvq_scan *s, int64_t out[9]);
  * out[0], out[2], out[3] are zero until the scan is finished and when it had no seed-filter launch.  The words are read
  * from the device when this is called; a scan that does not call it does nothing for it.  Returns 0 or an error code. */
 int32_t kvq_scan_match_info(const kvq_scan *s, int64_t out[4]);
+/* (measurement) the exact record index of one batch in device memory, as every scan makes it for the exhaustive kernels, the
+ * read-list route, the clip and the input passes -- the same checks, chunk table and kernels, on the scan's stream --, brought to
+ * the host: chunk_nrec_out[c] the complete records of chunk c (nchunks words), and of the first min(R, cap) records
+ * nl4_out[4 g + k] the batch offset of record g's k-th newline and rec_start_out[g] that of its first byte (the chunk's begin
+ * for a chunk's first record, else one behind the newline that ends the record in front).  The bytes are arbitrary: a record
+ * is four newlines.  d_text as for kvq_scan_device (16-byte aligned, readable up to the next multiple of 16 behind nbytes).
+ * Allowed only on a scan that holds no batch (before the first, or after kvq_scan_reset); it leaves no batch, hit or counter
+ * behind.  Returns R, the records of the batch, or -1 on an error (kvq_last_error).  The tests pin the index with it. */
+int64_t kvq_scan_index_device(kvq_scan *s, const void *d_text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                              uint32_t *nl4_out, uint32_t *rec_start_out, int64_t cap, uint32_t *chunk_nrec_out);
+/* (measurement) what the last seed-filter launch of a finished scan of ONE batch left to the redo of its skipped tiles.
+ * kvq_scan_set_keep_skipped(s, 1), before the first batch or after kvq_scan_reset, makes the scan keep host copies of both lists
+ * at the one place where it reads a batch's fail word; off (the default), nothing is copied and both calls below are errors.
+ * kvq_scan_skipped_tiles: the descriptors in the order kvq_validate_tiles wrote them, six words each -- a, b (the chunk, or from
+ * z - 1 on when the tile scanned the records in front of a record at z - 1), own_begin, own_end (the bytes whose newlines the tile
+ * owns), seen (newlines of [a, own_begin)), first (the record at `a` is the tile's too).  kvq_scan_redo_list: the entries
+ * kvq_collect_skipped put on the redo's list for them, nl4 and rec_start as in kvq_scan_index_device, in the order the atomics
+ * gave; the reads the scan kernel put there itself, already trimmed, are left out.  Both copy min(n, cap) entries and return n,
+ * or -1 on an error. */
+int32_t kvq_scan_set_keep_skipped(kvq_scan *s, int32_t on);
+int64_t kvq_scan_skipped_tiles(const kvq_scan *s, uint32_t *out, int64_t cap);
+int64_t kvq_scan_redo_list(const kvq_scan *s, uint32_t *nl4_out, uint32_t *rec_start_out, int64_t cap);
 int64_t kvq_scan_main_kernel_launches(const kvq_scan *s);
 /* forget accumulated hits/counters/timers but keep buffers (bench steps) */
 int32_t kvq_scan_reset(kvq_scan *s);

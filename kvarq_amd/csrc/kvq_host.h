@@ -172,6 +172,9 @@ struct kvq_scan {
     uint32_t surv_cap = 0;             // slots of d_surv's list (KVQ_SURV_CAP, or what the environment cut it to)
     DevBuf d_surv;                     // what passed the scan kernel's 16-base test, for kvq_verify_survivors (KvqSurvivors)
     DevBuf d_redo;                     // the redo of skipped tiles (KvqRedo: count, newline quadruples, record starts, trimmed reads)
+    bool keep_skipped = false;         // (measurement) kvq_scan_set_keep_skipped: redo_if_failed keeps host copies of the two lists below
+    std::vector<uint32_t> kept_tiles;  // the skipped-tile descriptors of the batch whose fail word was read last (six words each, as kvq_validate_tiles wrote them)
+    std::vector<uint32_t> kept_redo;   // what kvq_collect_skipped put on the redo list for them (five words each: rec_start, nl4)
     DevBuf d_seg_base, d_seg_cnt, d_chunk_nrec, d_rec_base, d_nl4, d_rec_start, d_read_off, d_read_len;
     // hit arena
     DevBuf d_covdiff;                  // coverage marks (KvqParams::covdiff)

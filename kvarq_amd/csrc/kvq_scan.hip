@@ -296,6 +296,7 @@ extern "C" int32_t kvq_scan_reset(kvq_scan *s)
     s->ms_all = s->ms_main = 0; for (KvqPass &p : s->passes) p.ms = 0;
     s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
     s->tail_pending = false;
+    s->kept_tiles.clear(); s->kept_redo.clear();
     s->pool.used = 0;
     const int rr = reset_device_state(s);
     if (g_timing) fprintf(stderr, "reset host %.3f ms\n", now_ms() - tr0);
@@ -607,6 +608,67 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
     return KVQ_OK;
 }
 
+// (measurement, kvq_scan_set_keep_skipped) host copies of what the batch's seed-filter launch left for the redo of its skipped tiles, taken
+// while the pool still holds them: the descriptors kvq_validate_tiles wrote (fail >> 8 of them) and the entries kvq_collect_skipped
+// put on the redo list (those the scan kernel put there itself, KVQ_REDO_TRIMMED, left out).  The batch's kernels are through.
+static int keep_skipped_lists(kvq_scan *s, unsigned int fail)
+{
+    s->kept_tiles.clear(); s->kept_redo.clear();
+    const size_t nt = std::min<size_t>(fail >> 8, KVQ_SKIP_CAP);
+    if (!nt || !s->cur_ntiles) return KVQ_OK;
+    const KvqRedo Rd(s->d_redo.p);
+    unsigned int cnt = 0;
+    s->kept_tiles.resize(nt * 6);
+    KVQ_HIP(hipMemcpyAsync(s->kept_tiles.data(), s->pool.d + s->cur_skip_at, nt * sizeof(KvqSkippedTile), hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipMemcpyAsync(&cnt, Rd.count, 4, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipStreamSynchronize(s->stream));
+    const size_t n = std::min<size_t>(cnt, KVQ_REDO_CAP - KVQ_LONG_CAP);
+    if (!n) return KVQ_OK;
+    std::vector<uint32_t> nl4(4 * n), rs(n);
+    KVQ_HIP(hipMemcpyAsync(nl4.data(), Rd.nl4, n * 16, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipMemcpyAsync(rs.data(), Rd.rec_start, n * 4, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipStreamSynchronize(s->stream));
+    for (size_t i = 0; i < n; i++) {
+        if (rs[i] == KVQ_REDO_TRIMMED) continue;
+        s->kept_redo.push_back(rs[i]);
+        s->kept_redo.insert(s->kept_redo.end(), nl4.begin() + 4 * i, nl4.begin() + 4 * i + 4);
+    }
+    return KVQ_OK;
+}
+extern "C" int32_t kvq_scan_set_keep_skipped(kvq_scan *s, int32_t on)
+{
+    kvq_clear_error();
+    if (const int rc = scan_idle(s, "kvq_scan_set_keep_skipped")) return rc;
+    s->keep_skipped = on != 0;
+    s->kept_tiles.clear(); s->kept_redo.clear();
+    return KVQ_OK;
+}
+static int kept_lists_ready(const kvq_scan *s, const char *who)
+{
+    if (s->keep_skipped && s->finished) return KVQ_OK;
+    kvq_set_error(KVQ_ERR_RUNTIME, "%s: only on a finished scan that kvq_scan_set_keep_skipped was turned on for", who);
+    return KVQ_ERR_RUNTIME;
+}
+extern "C" int64_t kvq_scan_skipped_tiles(const kvq_scan *s, uint32_t *out, int64_t cap)
+{
+    kvq_clear_error();
+    if (kept_lists_ready(s, "kvq_scan_skipped_tiles")) return -1;
+    const int64_t n = (int64_t)(s->kept_tiles.size() / 6);
+    if (out && cap > 0) memcpy(out, s->kept_tiles.data(), (size_t)std::min(n, cap) * 24);
+    return n;
+}
+extern "C" int64_t kvq_scan_redo_list(const kvq_scan *s, uint32_t *nl4_out, uint32_t *rec_start_out, int64_t cap)
+{
+    kvq_clear_error();
+    if (kept_lists_ready(s, "kvq_scan_redo_list")) return -1;
+    const int64_t n = (int64_t)(s->kept_redo.size() / 5);
+    for (int64_t i = 0; i < std::min(n, cap); i++) {
+        if (rec_start_out) rec_start_out[i] = s->kept_redo[5 * (size_t)i];
+        if (nl4_out) memcpy(nl4_out + 4 * i, &s->kept_redo[5 * (size_t)i + 1], 16);
+    }
+    return n;
+}
+
 // A batch's fail word, read once its kernels are through (the one place where it is read).  0: nothing.  Bit 0 clear: only some tiles were
 // skipped, and their records have been through the exhaustive kernels behind the scan (redo_skipped_tiles).  Bit 0 set: the seed-filter pass
 // failed validation (a tile's speculated record split disagreed with the newline count, one read flooded a wave's queues) and was rolled back
@@ -614,6 +676,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
 static int redo_if_failed(kvq_scan *s, size_t b, unsigned int fail, const uint8_t *text, bool *redone)
 {
     *redone = false;
+    if (s->keep_skipped) { if (const int rc = keep_skipped_lists(s, fail)) return rc; }
     if (!fail) return KVQ_OK;
     if (!(fail & 1u)) { s->path_bits |= 8 | 2; s->seen_skips = true; return KVQ_OK; }
     // (the redo's place on the list is the one batch number that check_batch has not seen: beyond the last range word there is no room for it)
@@ -639,6 +702,36 @@ static int check_batch(const void *data, int64_t nbytes, const int64_t *chunk_of
             kvq_set_error(KVQ_ERR_RUNTIME, "bad chunk offsets"); return KVQ_ERR_RUNTIME;
         }
     return KVQ_OK;
+}
+
+// (measurement) the exact record index of a batch, as run_batch makes it -- check_batch, chunk_table, index_records, on the scan's
+// stream -- brought to the host: the records per chunk, and the first `cap` records' nl4 (four words each) and rec_start.  Only on a
+// scan that holds no batch; it leaves none behind, and no hit or counter.  Returns the records of the batch, -1 on an error.
+extern "C" int64_t kvq_scan_index_device(kvq_scan *s, const void *d_text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                         uint32_t *nl4_out, uint32_t *rec_start_out, int64_t cap, uint32_t *chunk_nrec_out)
+{
+    kvq_clear_error();
+    if (scan_idle(s, "kvq_scan_index_device")) return -1;
+    if (nbytes <= 0 || nchunks <= 0) return 0;
+    if (check_batch(d_text, nbytes, chunk_off, nchunks, 0, true)) return -1;
+    BatchRun B;
+    B.d_data = (const uint8_t *)d_text; B.nbytes = nbytes; B.nchunks = nchunks; B.fpos_base = 0; B.batch_no = 0; B.use_seeded = false;
+    const size_t pool_used = s->pool.used;
+    auto run = [&]() -> int {
+        int rc;
+        if ((rc = chunk_table(s, B, chunk_off)) || (rc = index_records(s, B))) return rc;
+        const size_t n = (size_t)std::min<int64_t>(B.nrec, std::max<int64_t>(cap, 0));
+        if (chunk_nrec_out) KVQ_HIP(hipMemcpyAsync(chunk_nrec_out, s->d_chunk_nrec.p, (size_t)nchunks * 4, hipMemcpyDeviceToHost, s->stream));
+        if (n && nl4_out) KVQ_HIP(hipMemcpyAsync(nl4_out, s->d_nl4.p, n * 16, hipMemcpyDeviceToHost, s->stream));
+        if (n && rec_start_out) KVQ_HIP(hipMemcpyAsync(rec_start_out, s->d_rec_start.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+        KVQ_HIP(hipStreamSynchronize(s->stream));
+        KVQ_HIP(hipGetLastError());
+        return KVQ_OK;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(s->stream);
+    s->pool.used = pool_used;                      // (the stream is idle: the chunk table's place in the pool is free again)
+    return rc ? -1 : B.nrec;
 }
 
 extern "C" int32_t kvq_scan_device(kvq_scan *s, const void *d_data, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int64_t fpos_base)

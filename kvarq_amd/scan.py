@@ -241,6 +241,45 @@ class Scanner(object):
         _check(_lib.lib().kvq_scan_match_info(self.h, out))
         return dict(zip(self.MATCH_INFO, (int(x) for x in out)))
 
+    def index_device(self, d_ptr, nbytes, chunk_off, cap=None):
+        """(measurement) ``kvq_scan_index_device``: the exact record index of a batch in device memory -> (R, records per chunk,
+        nl4 as an (n, 4) array, rec_start), n = min(R, cap); ``cap`` None: a quarter of the batch's bytes, which holds any index"""
+        co = np.ascontiguousarray(chunk_off, dtype=np.int64)
+        cap = nbytes // 4 + 1 if cap is None else cap
+        nl4, rs, per = np.zeros((max(cap, 1), 4), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(len(co) - 1, 1), dtype=np.uint32)
+        R = _lib.lib().kvq_scan_index_device(self.h, d_ptr, nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+                                             nl4.ctypes.data, rs.ctypes.data, cap, per.ctypes.data)
+        if R < 0:
+            _raise_last()
+        n = min(R, cap)
+        return R, per[:len(co) - 1], nl4[:n], rs[:n]
+
+    def keep_skipped(self, on=True):
+        """(measurement) ``kvq_scan_set_keep_skipped``: keep what ``skipped_tiles`` and ``redo_list`` report"""
+        _check(_lib.lib().kvq_scan_set_keep_skipped(self.h, 1 if on else 0))
+
+    SKIPPED_TILE = ('a', 'b', 'own_begin', 'own_end', 'seen', 'first')
+
+    def skipped_tiles(self):
+        """(measurement) ``kvq_scan_skipped_tiles``: the descriptors of the finished scan's skipped tiles, an (n, 6) array"""
+        L = _lib.lib()
+        n = L.kvq_scan_skipped_tiles(self.h, None, 0)
+        if n < 0:
+            _raise_last()
+        out = np.zeros((max(n, 1), 6), dtype=np.uint32)
+        L.kvq_scan_skipped_tiles(self.h, out.ctypes.data, n)
+        return out[:n]
+
+    def redo_list(self):
+        """(measurement) ``kvq_scan_redo_list``: what kvq_collect_skipped left on the redo's list -> (nl4 (n, 4), rec_start)"""
+        L = _lib.lib()
+        n = L.kvq_scan_redo_list(self.h, None, None, 0)
+        if n < 0:
+            _raise_last()
+        nl4, rs = np.zeros((max(n, 1), 4), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32)
+        L.kvq_scan_redo_list(self.h, nl4.ctypes.data, rs.ctypes.data, n)
+        return nl4[:n], rs[:n]
+
     def hit_arrays(self):
         """the library's result arrays as numpy arrays (copies): seq_nr, file_pos, seq_pos, length, readlength,
         hitseq offsets (n + 1), hit bytes"""
