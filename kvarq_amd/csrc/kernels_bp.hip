@@ -359,7 +359,7 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
     __shared__ __align__(16) BpLds S;
     uint8_t *const lds_raw = reinterpret_cast<uint8_t *>(&S);
     int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t wave = rfl((uint32_t)tid >> 6);
+    const uint32_t wave_k = rfl((uint32_t)tid >> 6);
     if ((uint32_t)(uintptr_t)((__attribute__((address_space(3))) uint8_t *)lds_raw) != 0u) __builtin_trap();   // lds_u32_at
     unsigned long long stamp_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, stamp_t = 0, wave_p34 = 0;
     // (instrumented build: the workgroup's life on the constant 100 MHz clock -- entry, end of the prologue, end of its first tile, exit)
@@ -384,12 +384,12 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
         for (int i = tid; i < (1 << (2 * KK)) / 32; i += ST_THREADS) reinterpret_cast<uint32_t *>(S.bmA)[i] = bm1[i];
     }
     // the drawing wave (the last one, which holds the fewest reads) and its share of the tiles
-    uint32_t my_shard = blockIdx.x % BP_SHARDS; bool no_more = false;
-    if (wave == ST_WAVES - 1u) {
+    uint32_t my_shard = blockIdx.x % BP_SHARDS; uint32_t no_more = 0;         // (a word on the scalar unit, not a flag: as a flag it lived as a 64-bit lane mask, and so did its complement, both spilled)
+    if (wave_k == ST_WAVES - 1u) {
         unsigned int *const ctr = bp_args(A_)->tile_ctr;
         const uint32_t t0 = bp_draw_wave(ctr, ntiles, my_shard, (uint32_t)lane);
         const uint32_t t1 = t0 < ntiles ? bp_draw_wave(ctr, ntiles, my_shard, (uint32_t)lane) : ntiles;
-        no_more = t1 >= ntiles;
+        no_more = rfl(t1 >= ntiles ? 1u : 0u);
         if (lane == 0) { S.first_tile = t0; S.next_tile = t1; }
     }
     for (int i = tid; i < KVQ_RL_BINS / 2; i += ST_THREADS) S.hist[i] = 0;
@@ -421,18 +421,26 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
     for (uint32_t g = rfl(S.first_tile); ; ) {
         asm volatile("" : "+v"(tid));
         lane = tid & 63;
+        // (the wave's number, new to the compiler in every tile: what hangs on it -- its stretch's ends, the masks of "wave 0" and "the last
+        // wave" -- is worked out in the tile on the scalar unit, not carried round the tile loop in spilled lanes)
+        uint32_t wave = wave_k;
+        asm volatile("" : "+s"(wave));
         const uint32_t blk = (uint32_t)tid * ST_BLK;                           // the thread's newline block in the window
         const uint32_t wv = wave * (ST_BLK * 64u / 16u) + (uint32_t)lane;      // the lane's vector of round 0
         if constexpr (STAMPS) stamp_t = __builtin_amdgcn_s_memtime();
         // tile geometry (the per-tile table kvq_expand_tiles wrote: chunk begin, chunk end, tile number)
-        uint32_t Ja = 0, Jb = 0, Jt = 0, g0 = 0; GlbBytes text = nullptr;
+        // (no branch round this: behind the text's last tile a workgroup works the geometry of that tile out once more and "loads" from a
+        // buffer of no bytes -- zeros, no trip to memory -- and leaves at the barrier below.  With the branch every value set here had a
+        // second, empty definition to be merged with: the resource words, the text pointer and the test itself went through spilled lanes)
+        uint32_t Ja, Jb, Jt, g0; GlbBytes text;
         uint4 pre[ST_ROUNDS];
-#pragma unroll
-        for (int r = 0; r < (int)ST_ROUNDS; r++) pre[r] = make_uint4(0, 0, 0, 0);      // (no "value of the last tile" for the compiler to keep alive through the whole tile)
-        if (g < ntiles) {
+        {
             const BpArgsPtr A = bp_args(A_);
+            uint32_t gi = g < ntiles ? g : ntiles - 1u;
+            uint32_t rs_flags = 0x00020000u;
+            asm volatile("" : "+s"(gi), "+s"(rs_flags));                    // (a 32-bit index and a constant made here: carried round the tile loop as a 64-bit index and a resource word, both were spilled)
             // (diagnostic 64: every tile scans the text of one of the first 64 tiles -- the same work from L2 instead of HBM; results are wrong)
-            const u32x4_t q = ((const __attribute__((address_space(4))) u32x4_t *)A->tiles)[(dbg & 64u) ? (g & 63u) : g];
+            const u32x4_t q = ((const __attribute__((address_space(4))) u32x4_t *)A->tiles)[(dbg & 64u) ? (gi & 63u) : gi];
             Ja = q.x; Jb = q.y; Jt = q.z;
             g0 = (Ja & ~15u) + Jt * tile_bytes;
             const uint8_t *const data = A->data;
@@ -442,7 +450,7 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
             // the text: vectors 0..4 never hold text, an offset beyond any tile makes their load return zeros;
             // all of the offset in the checked part: the range check leaves the scalar offset out)
             const uint32_t vo = 16u * wv - ST_PRE, vo0 = wv >= ST_PRE / 16u ? vo : ST_NO_BLOCK;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(data + g0), 0, (int)(((load_hi + 15u) & ~15u) - g0), 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(data + g0), 0, g < ntiles ? (int)(((load_hi + 15u) & ~15u) - g0) : 0, (int)rs_flags);
 #pragma unroll
             for (int r = 0; r < (int)ST_ROUNDS; r++) {
                 const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(r ? vo + 1024u * r : vo0), 0, KVQ_TEXT_AUX);
@@ -674,269 +682,31 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
         }
         const uint32_t G = 1u << lg, RP = ST_THREADS >> lg;
         const uint32_t gl = (uint32_t)tid & (G - 1u), gr = (uint32_t)tid >> lg;
-        for (uint32_t pass0 = 0; pass0 < nrec; pass0 += RP) {
-            const uint32_t k = pass0 + gr;
-            const bool have = k < nrec;
-            uint32_t roff = 0; int rl = 0;
-            uint32_t c0, cp;                                        // the record's '@' and '+' (1037-1048): fetched here by the group's first lane, looked at behind the pass
-            if (have) {
-                const uint32_t m = jn + 4u * k;
-                const uint32_t rstart = m == 0 ? ST_PRE + (Ja & 15u) : (uint32_t)S.nl[m - 1] + 1u;
-                const uint32_t n0 = S.nl[m], n1 = S.nl[m + 1], n2 = S.nl[m + 2], n3 = S.nl[m + 3];
-                const uint32_t sread = n0 + 1u, plus = n1 + 1u, sscore = n2 + 1u;
-        KVQ_MARK("trim");
-                if (gl == 0) { if (dbg & 8u) { c0 = '@'; cp = '+'; } else { c0 = text[rstart]; cp = text[plus]; } }   // (diagnostic 8: no '@' / '+' probes -- ablation only)
-                // quality trim (1055-1068): this lane's slice of the score line is a bit range of the good plane
-                const int Q = (int)(n3 - sscore);                   // the closing '\n' is implied
-                const int per = (Q + (int)G - 1) >> lg;
-                Seg sg; sg.beg = (int)mul_u24(gl, (uint32_t)per); if (sg.beg > Q) sg.beg = Q;
-                int s1 = sg.beg + per; if (s1 > Q) s1 = Q;
-                sg.len = 0; sg.pre = 0; sg.suf = 0; sg.best = 0; sg.bstart = sg.beg;
-                {
-                    // one round of at most 64 score bits
-                    auto round = [&](int c0_) -> Seg {
-                        const int n = s1 - c0_ < 64 ? s1 - c0_ : 64;
-                        const uint32_t bit = sscore + (uint32_t)c0_;
-                        const uint32_t a = BP_LDS_GDP + ((bit >> 5) << 2), sh = bit & 31u;
-                        const uint32_t d0 = lds_u32_at(a), d1 = lds_u32_at(a + 4u), d2 = lds_u32_at(a + 8u);
-                        const uint64_t nmask = n < 64 ? (1ull << n) - 1ull : ~0ull;
-                        const uint64_t mm = (((uint64_t)__builtin_amdgcn_alignbit(d2, d1, sh) << 32) | (uint64_t)__builtin_amdgcn_alignbit(d1, d0, sh)) & nmask;
-                        Seg sub; sub.beg = c0_; sub.len = n;
-                        int bs;
-                        bp_runs64(mm, n, dbg, sub.pre, sub.suf, sub.best, bs);
-                        sub.bstart = c0_ + bs;
-                        return sub;
-                    };
-                    if (!__any(per > 64)) sg = round(sg.beg);
-                    else {
-                        for (int cc = sg.beg; cc < s1; cc += 64) {
-                            const Seg sub = round(cc);
-                            sg = (cc == sg.beg) ? sub : seg_merge(sg, sub);
-                        }
-                    }
-                }
-                // ordered tree merge over the G lanes of the read
-                if (G == 4u) {
-#define KVQ_QUAD(v, ctl) __builtin_amdgcn_update_dpp(0, (v), (ctl), 0xf, 0xf, true)
-                    {
-                        Seg B;                                                       // lane ^ 1: quad_perm [1,0,3,2]
-                        B.len = KVQ_QUAD(sg.len, 0xB1); B.pre = KVQ_QUAD(sg.pre, 0xB1); B.suf = KVQ_QUAD(sg.suf, 0xB1);
-                        B.best = KVQ_QUAD(sg.best, 0xB1); B.bstart = KVQ_QUAD(sg.bstart, 0xB1); B.beg = 0;
-                        sg = seg_merge(sg, B);
-                    }
-                    {
-                        Seg B;                                                       // lane ^ 2: quad_perm [2,3,0,1]
-                        B.len = KVQ_QUAD(sg.len, 0x4E); B.pre = KVQ_QUAD(sg.pre, 0x4E); B.suf = KVQ_QUAD(sg.suf, 0x4E);
-                        B.best = KVQ_QUAD(sg.best, 0x4E); B.bstart = KVQ_QUAD(sg.bstart, 0x4E); B.beg = 0;
-                        sg = seg_merge(sg, B);
-                    }
-                    rl = KVQ_QUAD(sg.best, 0x00);
-                    roff = sread + (uint32_t)KVQ_QUAD(sg.bstart, 0x00);              // 1070
-#undef KVQ_QUAD
-                } else {
-                    for (uint32_t d = 1; d < G; d <<= 1) {
-                        Seg B;
-                        B.len = __shfl_xor(sg.len, (int)d, 64); B.pre = __shfl_xor(sg.pre, (int)d, 64); B.suf = __shfl_xor(sg.suf, (int)d, 64);
-                        B.best = __shfl_xor(sg.best, (int)d, 64); B.bstart = __shfl_xor(sg.bstart, (int)d, 64); B.beg = 0;
-                        if ((gl & d) == 0) sg = seg_merge(sg, B);
-                    }
-                    rl = __shfl(sg.best, lane & ~(int)(G - 1u), 64);
-                    roff = sread + (uint32_t)__shfl(sg.bstart, lane & ~(int)(G - 1u), 64);             // 1070
-                }
-                // (the longest read: a running maximum per lane, put together once at the end of the kernel -- an
-                // atomic maximum in LDS per read is turned into a scalar loop over the wave's lanes by the compiler)
-                my_longest = my_longest > (uint32_t)(rl + 1) ? my_longest : (uint32_t)(rl + 1);
-                if (gl == 0) {
-                    if (rl < KVQ_RL_BINS) atomicAdd(&S.hist[rl >> 1], 1u << (16 * (rl & 1)));          // 394-402
-                    S.rinfo[k] = roff | ((uint32_t)rl << 16);
-                }
+        // The pass body (kernels_bp_pass.inc) stands here twice.  A tile of sequencer records is ONE pass of ONE stretch per wave with ONE
+        // window of work items: the straight body says so -- no pass loop, no stretch loop, no window loop, so nothing of the tile is
+        // carried round a loop whose trip count the compiler cannot know (that was 31 of 73 spilled scalars).  A wave leaves it, before it
+        // has emitted or queued anything for good, when a queue overflows or its work items outgrow their window, and takes the loops
+        // from the pass's beginning (`recount`: its reads are in the histogram already).  Tiles of more records than a pass holds, the
+        // draining kernels and the kernel that works the lane group out per tile know the loops only.
+        bool loops = true, recount = false;
+        if constexpr (LG >= 0 && !DENSE) {
+            if (nrec <= RP) {
+                bool bail = false;                                  // (wave-uniform)
+#define BP_STRAIGHT 1
+#define BP_SFX ""
+#include "kernels_bp_pass.inc"
+#undef BP_STRAIGHT
+#undef BP_SFX
+                loops = recount = bail;
             }
-        KVQ_MARK("trim end / filter");
-            BSTAMP(4);
-            KVQ_SETPRIO(2);
-            // filter + verify, wave by wave (the wave's reads, candidates and work items are its own)
-            const uint32_t rpw = 64u >> lg, grw = (uint32_t)lane >> lg;
-            const uint32_t wfirst = pass0 + wave * rpw;
-            const uint32_t npass = wfirst < nrec ? (nrec - wfirst < rpw ? nrec - wfirst : rpw) : 0u;
-            uint32_t *const q1 = S.q1 + wave * BP_QW; uint32_t *const q2 = S.q2 + wave * BP_Q2W;
-            uint32_t sub = (dbg & 128u) ? npass : 0u, step = rpw;             // (diagnostic 128: trim only)
-            while (sub < npass) {
-                BTALLY(6, lane == 0);
-                // (a stretch is one turn of this loop unless a queue overflows; what depends on the read only is worked out here, where it is
-                // wanted, not hoisted in front of the loop into a dozen registers and spilled wave masks: the compiler cannot know the trip count)
-                asm volatile("" : "+v"(rl), "+v"(roff));
-                int minrl, me_; const __attribute__((address_space(1))) uint8_t *bmL;
-                {
-                    const BpArgsPtr A = bp_args(A_);
-                    minrl = A->P.minreadlength; me_ = A->P.maxerrors;
-                    bmL = (const __attribute__((address_space(1))) uint8_t *)A->X.bm1 + (1 << (2 * KK)) / 8;
-                }
-                const bool mine = have && rl >= minrl && !(dbg & 2u) && grw >= sub && grw - sub < step;       // 1100
-                uint32_t qn = 0;
-                int e0 = 0, e1 = 0;
-                if (mine) {
-                    const int NPe = (rl - KK) / SS + 1;
-                    const int per = (NPe + (int)G - 1) >> lg;
-                    e0 = (int)mul_u24(gl, (uint32_t)per); if (e0 > NPe) e0 = NPe;
-                    e1 = e0 + per; if (e1 > NPe) e1 = NPe;
-                }
-                // is the 8-mer at read position pp anywhere in a sequence?  (bitmap of all sequence 8-mers: global memory)
-                // (the load is issued whether the block is wanted or not -- any code has its byte in the bitmap --
-                // so that the two lookups of a lane travel together instead of each behind a branch of its own)
-                auto fixed_block = [&](int pp, bool ok) -> bool {
-                    const uint32_t code = cdp_code<KK>(roff + (uint32_t)(ok ? pp : 0));
-                    const uint32_t bits = bmL[code >> 3];
-                    return ok & (bool)((bits >> (code & 7u)) & 1u);
-                };
-                auto head_ok = [&](int jj) { return mine && jj <= me_ && (jj + 1) * KK <= rl; };
-                auto tail_ok = [&](int jj) { const int pp = rl - (jj + 1) * KK; return mine && jj <= me_ && pp >= 0 && !((pp % KK) == 0 && pp <= me_ * KK); };
-                const bool hhit = fixed_block((int)gl * KK, head_ok((int)gl));
-                const bool thit = fixed_block(rl - ((int)gl + 1) * KK, tail_ok((int)gl));
-                constexpr int NR = SS == 8 ? 6 : SS == 4 ? 12 : (LG == 3 || LG == 1) ? 24 : 18;  // lookups per lane and round (18: a 150-base read's 72 even positions over four lanes; 24: a 300-base read's 147 over eight -- 19 a lane -- or a 100-base read's 47 over two, one round instead of two)
-                bool first = true;
-                if constexpr (!DENSE) {
-                for (int ee = e0; __any(ee < e1); ee += NR, first = false) {
-                    const bool act = ee < e1;
-#include "kernels_bp_lookup.inc"
-                    const int nv = act ? (e1 - ee < NR ? e1 - ee : NR) : 0;
-                    hA &= (1u << nv) - 1u;                                      // nv <= 24
-                    const bool hh = first && hhit, th = first && thit;
-                    const uint32_t c = (uint32_t)__popc(hA) + (hh ? 1u : 0u) + (th ? 1u : 0u);
-                    const uint32_t inc = kvq_wave_incl_scan(c);
-                    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-                    if (tot) {
-                        uint32_t idx = qn + inc - c;
-                        while (hA) {
-                            const int j = __ffs((int)hA) - 1; hA &= hA - 1u;
-                            if (idx < BP_QW) q1[idx] = k | ((uint32_t)(SS * (ee + j)) << 9);        // beyond the cap: dropped, the stretch is redone in halves
-                            idx++;
-                        }
-                        if (hh) { if (idx < BP_QW) q1[idx] = k | ((gl * KK) << 9) | (1u << BP_Q1_KIND); idx++; }
-                        if (th && idx < BP_QW) { const uint32_t pt = (uint32_t)(rl - ((int)gl + 1) * KK); q1[idx] = k | (pt << 9) | (1u << BP_Q1_KIND); }
-                        qn += tot;
-                    }
-                }
-                // groups narrower than e+1 lanes: the remaining head and tail blocks, one push round each
-                for (int t = (int)G; t <= me_; t += (int)G) {
-                    const int jj = t + (int)gl;
-#pragma unroll
-                    for (int side = 0; side < 2; side++) {
-                        const int pp = side ? rl - (jj + 1) * KK : jj * KK;
-                        const bool hit = fixed_block(pp, side ? tail_ok(jj) : head_ok(jj));
-                        const uint64_t mm = __ballot(hit);
-                        if (mm) {
-                            const uint32_t idx = qn + (uint32_t)__popcll(mm & kvq_lanemask_lt());
-                            if (hit && idx < BP_QW) q1[idx] = k | ((uint32_t)pp << 9) | (1u << BP_Q1_KIND);
-                            qn += (uint32_t)__popcll(mm);
-                        }
-                    }
-                }
-                }   // !DENSE
-        KVQ_MARK("filter end / P4a");
-                BSTAMP(5);
-                KVQ_SETPRIO(3);
-
-                // ---- P4: candidates -> (candidate, index entry) work items, one per lane -> a window of sixteen bases of the diagonal
-                // as 2-bit codes against the entry's own copy of the sequence around the seed (SeedEntry::ctx; equal bytes have equal
-                // codes, so this only ever rejects, and nearly every false candidate ends here: TWO dependent loads, code -> range of
-                // entries -> entry; round 3 went on to the 2-bit table for the bases) -> what is left goes through bp_verify_rest ----
-                if constexpr (!DENSE) {
-                const bool over = qn > BP_QW;                             // candidates were dropped
-                const uint32_t qn_ok = (over || (dbg & 1u)) ? 0u : qn;
-                if (over && step > 1u) { step >>= 1; continue; }
-                if (over) {
-                    // ONE read has more candidates than the queue holds (step == 1): it alone goes to the exhaustive matcher behind the scan (the redo's
-                    // list: trimmed and counted here, KVQ_REDO_TRIMMED), its tile carries on; a full list fails the batch
-                    if (mine && gl == 0) {
-                        const BpArgsPtr A = bp_args(A_);
-                        const KvqRedo Rd(A->redo);
-                        const uint32_t boff = g0 - ST_PRE + roff;
-                        bool put = false;
-                        if (A->redo) {
-                            if (rl >= KVQ_LONG_READ) {
-                                const unsigned int i = atomicAdd(Rd.count + 1, 1u);
-                                if (i < KVQ_LONG_CAP) { Rd.read_off[KVQ_REDO_CAP - 1u - i] = boff; Rd.read_len[KVQ_REDO_CAP - 1u - i] = rl; put = true; }
-                            }
-                            if (!put) {
-                                const unsigned int i = atomicAdd(Rd.count, 1u);
-                                if (i < A->redo_cap) { Rd.rec_start[i] = KVQ_REDO_TRIMMED; Rd.read_off[i] = boff; Rd.read_len[i] = rl; }
-                                put = true;                                  // (beyond the cap: kvq_dev_count fails the batch)
-                            }
-                        }
-                        if (!put) S.fallback = 1u;
-                        else atomicOr(A->fail, 2u);                      // (reported as records that went through the exhaustive kernels; the next launches of this scan object use the wide grids)
-                    }
-                }
-#include "kernels_bp_p4.inc"
-                } else {
-                    // ---- dense tables, short seeds: candidates by the dozen per read (round 4).  Nothing is dropped and nothing filtered twice:
-                    // the lanes push what a round of lookups found as far as the queue has room, the queue is drained (the work items of its
-                    // candidates verified), and the pushing goes on where it stopped; the sparse kernel halves the stretch and filters it again
-                    // when a queue overflows -- up to six times per stretch with the MTBC table x 8 ----
-                    uint32_t hA = 0, hpos = 0, tpos = 0; bool hh = false, th = false;
-                    int ee = e0, xt = (int)G;
-                    int ee_of_hA = e0;                                          // the round the pending anchor bits belong to
-                    bool done = false;
-                    while (!done) {
-                        bool full = false;
-                        while (!full) {
-                            if (!__any(hA != 0u || hh || th)) {
-                                // nothing pending: the next round of lookups (spelled out here, not a lambda: what a lambda captures by reference lives in scratch memory)
-                                ee_of_hA = ee;
-                                if (__any(ee < e1)) {
-                                    const bool act = ee < e1;
-                                    uint32_t hA_;
-                                    {
-#include "kernels_bp_lookup.inc"
-                                        hA_ = hA;
-                                    }
-                                    const int nv = act ? (e1 - ee < NR ? e1 - ee : NR) : 0;
-                                    hA = hA_ & ((1u << nv) - 1u);
-                                    if (first) { hh = hhit; th = thit; hpos = gl * KK; tpos = (uint32_t)(rl - ((int)gl + 1) * KK); first = false; }
-                                    ee += NR;
-                                } else if (xt <= me_) {                             // groups narrower than e + 1 lanes: the remaining head and tail blocks
-                                    const int jj = xt + (int)gl;
-                                    hpos = (uint32_t)(jj * KK); tpos = (uint32_t)(rl - (jj + 1) * KK);
-                                    hh = fixed_block((int)hpos, head_ok(jj)); th = fixed_block((int)tpos, tail_ok(jj));
-                                    xt += (int)G;
-                                } else { done = true; break; }
-                                continue;
-                            }
-                            const uint32_t c = (uint32_t)__popc(hA) + (hh ? 1u : 0u) + (th ? 1u : 0u);
-                            const uint32_t inc = kvq_wave_incl_scan(c);
-                            const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-                            uint32_t idx = qn + inc - c;
-                            while (hA && idx < BP_QW) {
-                                const int j = __ffs((int)hA) - 1; hA &= hA - 1u;
-                                q1[idx++] = k | ((uint32_t)(SS * (ee_of_hA + j)) << 9);
-                            }
-                            if (hh && idx < BP_QW) { q1[idx++] = k | (hpos << 9) | (1u << BP_Q1_KIND); hh = false; }
-                            if (th && idx < BP_QW) { q1[idx++] = k | (tpos << 9) | (1u << BP_Q1_KIND); th = false; }
-                            full = qn + tot >= BP_QW;
-                            qn = qn + tot < BP_QW ? qn + tot : BP_QW;
-                        }
-                        {
-                            const uint32_t qn_ok = (dbg & 1u) ? 0u : qn;
-#include "kernels_bp_p4.inc"
-                        }
-                        qn = 0;
-                    }
-                }
-                KVQ_SETPRIO(2);
-                sub += step;
-            }
-            KVQ_SETPRIO(0);
-            // the '@' / '+' checks of the pass's records (the bytes have come back long ago)
-            if (have && gl == 0 && (c0 != '@' || cp != '+')) {          // (lanes that fetched nothing never look)
-                const BpArgsPtr A = bp_args(A_);
-                const uint32_t m = jn + 4u * k;
-                const uint32_t rstart = m == 0 ? ST_PRE + (Ja & 15u) : (uint32_t)S.nl[m - 1] + 1u, plus = (uint32_t)S.nl[m + 1] + 1u;
-                const int64_t tf = A->fpos_base + (int64_t)g0;
-                if (c0 != '@') atomicMin(A->P.err, ((unsigned long long)(tf + rstart - ST_PRE) << 16) | (0ull << 8) | c0);
-                else atomicMin(A->P.err, ((unsigned long long)(tf + plus - ST_PRE) << 16) | (1ull << 8) | cp);
-            }
-        KVQ_MARK("P4 end");
-            BSTAMP(6);
+        }
+        if (loops) {
+            bool bail = false; (void)bail;
+#define BP_STRAIGHT 0
+#define BP_SFX " (loops)"
+#include "kernels_bp_pass.inc"
+#undef BP_STRAIGHT
+#undef BP_SFX
         }
         if constexpr (STAMPS) wave_p34 += __builtin_amdgcn_s_memtime() - wave_t3;
         // everyone is done with the tile's planes before the next tile's fill
@@ -945,7 +715,7 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
             uint32_t d = no_more ? ntiles : rfl(drawn);
             if (!no_more && d >= bp_shard_begin(my_shard + 1u, ntiles)) {
                 d = bp_draw_wave(bp_args(A_)->tile_ctr, ntiles, my_shard, (uint32_t)tid & 63u);
-                no_more = d >= ntiles;
+                no_more = rfl(d >= ntiles ? 1u : 0u);
             }
             if ((tid & 63) == 0) S.next_tile = d;
         }
@@ -959,7 +729,7 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
     if constexpr (STAMPS) rt_loop = __builtin_amdgcn_s_memrealtime();
     {
         // what is left of the wave's chunk of the survivors' list is marked dead (read length 0: kvq_verify_survivors skips it)
-        const uint32_t at = S.sv_at[wave], end = S.sv_end[wave];
+        const uint32_t at = S.sv_at[wave_k], end = S.sv_end[wave_k];
         if (at + (uint32_t)lane < end) KvqSurvivors(bp_args(A_)->surv).item[at + (uint32_t)lane].rl = 0;
     }
     atomicMax(&S.longest_p1, my_longest);
@@ -968,7 +738,7 @@ kvq_scan_bp(const BpArgs *__restrict__ A_)
     if constexpr (STAMPS) {
         if (tid == 0) for (int i = 0; i < 8; i++) atomicAdd(&ctr[KVQ_CTR_RL_ + 900 + i], stamp_acc[i]);
         for (int i = 0; i < 8; i++) if (tally[i]) atomicAdd(&ctr[KVQ_CTR_RL_ + 930 + i], (unsigned long long)tally[i]);
-        if (lane == 0) atomicAdd(&ctr[KVQ_CTR_RL_ + 908 + wave], wave_p34);
+        if (lane == 0) atomicAdd(&ctr[KVQ_CTR_RL_ + 908 + wave_k], wave_p34);
         if (tid == 0) {
             const unsigned long long rt_out = __builtin_amdgcn_s_memrealtime();
             atomicAdd(&ctr[KVQ_CTR_RL_ + 916], rt_pro - rt_in); atomicAdd(&ctr[KVQ_CTR_RL_ + 917], rt_first ? rt_first - rt_pro : 0ull);

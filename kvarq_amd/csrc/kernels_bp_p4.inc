@@ -1,6 +1,7 @@
 // kernels_bp_p4.inc -- P4 of kvq_scan_bp: the wave's qn_ok queued candidates -> work items -> 16-base window test -> bp_verify_rest
-// (textually included twice: the halving kernels run it once per stretch, the draining ones whenever their queue is full).
-// in: qn_ok, q1, q2, me_, lane, text, g0, S, A_
+// (textually included by kernels_bp_pass.inc: the halving kernels run it once per stretch, the draining ones whenever their queue is full).
+// BP_STRAIGHT 1: one window of work items and no loop round it; more than BP_Q2W of them set `bail` and nothing is tested
+// in: qn_ok, q1, q2, me_, lane, text, g0, S, A_, bail
                 if (qn_ok) {
                     typedef const __attribute__((address_space(1))) u32x4_t *GlbEntries;
                     typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
@@ -14,7 +15,12 @@
                     // (the items are numbered in candidate order; the queue takes BP_Q2W of them a round -- one round, unless a read matches
                     // dozens of sequences of a dense table: then the candidates, a hundred at most, are simply walked again for the next window)
                     BTALLY(5, lane == 0);
+#if BP_STRAIGHT
+                    {
+                        const uint32_t w0 = 0;
+#else
                     for (uint32_t w0 = 0; ; w0 += BP_Q2W) {
+#endif
                         uint32_t run = 0;
                         for (uint32_t q0 = 0; q0 < qn_ok; q0 += 64u) {
                             const uint32_t qi = q0 + lane;
@@ -32,8 +38,13 @@
                                 if (base + j < BP_Q2W) q2[base + j] = (qi << 22) | (en0 + j);
                             run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
                         }
-        KVQ_MARK("P4b");
+        KVQ_MARK("P4b" BP_SFX);
+#if BP_STRAIGHT
+                        if (run > BP_Q2W) bail = true;                          // (more work items than one window: the loops walk them)
+                        const uint32_t n_items = bail ? 0u : run;
+#else
                         const uint32_t n_items = run - w0 < BP_Q2W ? run - w0 : BP_Q2W;
+#endif
                         for (uint32_t i0 = 0; i0 < n_items; i0 += 64u) {
                             BTALLY(4, lane == 0);
                             const uint32_t ii = i0 + lane;
@@ -113,6 +124,8 @@
                                 }
                             }
                         }
+#if !BP_STRAIGHT
                         if (run <= w0 + BP_Q2W) break;
+#endif
                     }
                 }
