@@ -452,6 +452,44 @@ const int64_t *kvq_scan_clip(const kvq_scan *s);
 int32_t        kvq_clip_host(uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
                              const uint8_t *const *probes, const int32_t *lens, int32_t n, int64_t *out);
 
+/* ---- adapter probes that tolerate mismatches: ONE INTEGER, per, FOR THE CONTENT PASS AND THE CLIP ----
+ * per == 0 is the rule of the two sections above, word for word.  Otherwise 10 <= per <= 32 (KVQ_ADAPT_MIN_PER ..
+ * KVQ_ADAPT_MAX_PER), and a comparison over `len` bases may differ from the probe in at most E(len) = len / per positions
+ * (integer division).  per = 10 is cutadapt's default rate; the lower bound keeps E <= 3 and every tail shorter than 10 bases
+ * exact.
+ * WHAT COUNTS AS A MISMATCH: a position differs when the line's byte is not the probe's byte.  'N', a lower-case letter, '.' and
+ * a byte with the high bit set are each one mismatch; they are no match merely because they share a 2-bit code with a base.
+ * ham(a, b): the number of positions at which two byte strings of the same length differ.
+ * Everything else is the adapter content's: the record set, and L as the bases line without a trailing '\r'.
+ * FIRST_k: the smallest p with p + m_k <= L and ham(line[p, p + m_k), probe_k) <= E(m_k) -- the smallest p, not the p with the
+ * fewest mismatches.  The window lies inside the line: the bytes behind L (the '\r', the newline, whatever a kernel loads behind
+ * them) are mismatches like any other, and without the bound p + m_k <= L a window that hangs over the end by E bases would be
+ * accepted.  DIST_k: the number of differing positions of that window, 0 .. 3.
+ * TAIL_k: considered only when there is no FIRST_k under this same rule: the largest t with T <= t <= min(m_k - 1, L) and
+ * ham(line[L - t, L), probe_k[0, t)) <= E(t) -- E of t, not of m_k; the largest t wins even where a smaller t matches exactly.
+ * CLIP, MASK and the words of both arrays are as they are, with these additions, written only when per > 0 (with per == 0 they
+ * stay 0 and both arrays are the exact rule's, bit for bit):
+ *   adapters array [4] = per;   its blocks' words +4 .. +7 = the records with FIRST_k whose DIST_k is 0, 1, 2, 3 (they sum to +1);
+ *   clip array [5] = per.
+ * WHAT A LOOSER RULE COSTS: on uniformly random bases one 12-base probe matches a 150-base read somewhere with probability about
+ * 6.7e-4 at per = 10 against 3.3e-4 exact (the tails of 6 .. 9 bases, which stay exact, are half of it).  Measured on the CPU,
+ * 20 000 random reads against four 12-base probes: a clipped share of 0.14 % exact and 0.32 % at per = 10 (beside T's 0.03 % a
+ * probe above).
+ * kvq_scan_set_adapter_mismatches: one value per scan, for the adapter content and the clip alike; before the first batch or
+ * after kvq_scan_reset, as kvq_scan_set_cycles; in any order against kvq_scan_set_adapters and kvq_scan_set_clip (it needs
+ * neither, and stays while they go on and off); KVQ_ERR_RUNTIME outside {0} and [10, 32].  kvq_scan_adapter_mismatches: the
+ * value.  With per > 0 the passes launch kvq_adapt_records_mm / kvq_clip_records_mm (kernels_adapt_mm.hip) in place of the exact
+ * kernels, and kvq_scan_adapt_kernel_ms / kvq_scan_clip_kernel_ms report whichever ran. */
+enum { KVQ_ADAPT_PER = 4, KVQ_ADAPT_B_DIST = 4, KVQ_ADAPT_DISTS = 4, KVQ_CLIP_PER = 5, KVQ_ADAPT_MIN_PER = 10, KVQ_ADAPT_MAX_PER = 32 };
+int32_t        kvq_scan_set_adapter_mismatches(kvq_scan *s, int32_t per);
+int32_t        kvq_scan_adapter_mismatches(const kvq_scan *s);
+/* host only, plain C++: the CPU twins of kvq_adapt_records_mm and kvq_clip_records_mm -- the argument lists of kvq_adapt_host and
+ * kvq_clip_host plus per (outside {0} and [10, 32]: KVQ_ERR_RUNTIME).  With per == 0 they give the results of those two. */
+int32_t        kvq_adapt_host_mm(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                 const uint8_t *const *probes, const int32_t *lens, int32_t n, int32_t per, int64_t *out);
+int32_t        kvq_clip_host_mm(uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                const uint8_t *const *probes, const int32_t *lens, int32_t n, int32_t per, int64_t *out);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -461,8 +499,8 @@ double  kvq_scan_profile_kernel_ms(const kvq_scan *s);   /* ... and for kvq_prof
 double  kvq_scan_cycles_kernel_ms(const kvq_scan *s);    /* ... and for kvq_profile_cycles alone (0 when the cycles are off) */
 double  kvq_scan_reads_kernel_ms(const kvq_scan *s);     /* ... and for kvq_reads_records and the table's settle kernels (0 when both are off) */
 double  kvq_scan_over_kernel_ms(const kvq_scan *s);      /* ... and for kvq_over_records alone (0 when the overrepresented sequences are off) */
-double  kvq_scan_adapt_kernel_ms(const kvq_scan *s);     /* ... and for kvq_adapt_records alone (0 when the adapters are off) */
-double  kvq_scan_clip_kernel_ms(const kvq_scan *s);      /* ... and for kvq_clip_records alone (0 when the clip is off) */
+double  kvq_scan_adapt_kernel_ms(const kvq_scan *s);     /* ... and for kvq_adapt_records or kvq_adapt_records_mm alone, whichever ran (0 when the adapters are off) */
+double  kvq_scan_clip_kernel_ms(const kvq_scan *s);      /* ... and for kvq_clip_records or kvq_clip_records_mm alone (0 when the clip is off) */
 /* (measurement) ms between the end of a's last main kernel and the start of b's first one; both finished, not reset since */
 double  kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b);
 /* (measurement) how kvq_scan_finish put the hits of the finished scan in order:
@@ -656,6 +694,15 @@ typedef struct kvq_find_opts_adapters {
  * probe block there is: with KVQ_FIND_ADAPTERS too, both take the same probes.  Refused ("bad size") when base.size does not
  * cover that structure.  It is not tied to KVQ_FIND_PROFILE. */
 #define KVQ_FIND_CLIP 2048u
+/* KVQ_FIND_ADAPTER_MISMATCHES: kvq_scan_set_adapter_mismatches(mismatch_per) for the call.  The value rides behind the probes in
+ * a structure that begins with kvq_find_opts_adapters, read only with the flag and only when base.size covers it -- otherwise
+ * "bad size"; the 20-byte and the 288-byte structures keep their meaning.  The flag without KVQ_FIND_ADAPTERS or KVQ_FIND_CLIP is
+ * KVQ_ERR_RUNTIME. */
+#define KVQ_FIND_ADAPTER_MISMATCHES 4096u
+typedef struct kvq_find_opts_adapters_mm {
+    kvq_find_opts_adapters a;            /* a.base.size: sizeof(kvq_find_opts_adapters_mm) */
+    int32_t  mismatch_per;
+} kvq_find_opts_adapters_mm;
 kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
                             const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts);
 

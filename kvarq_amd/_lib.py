@@ -20,6 +20,7 @@ FIND_READ_STATS, FIND_DUPLICATION = 128, 256                     # ... the per-r
 FIND_OVERREPRESENTED = 512                                       # ... the overrepresented sequences (with FIND_PROFILE)
 FIND_ADAPTERS = 1024                                             # ... the adapter content (with FIND_PROFILE; the probes in FindOptsAdapters)
 FIND_CLIP = 2048                                                 # ... the adapter clip ahead of the trim (no profile needed; the same probe block)
+FIND_ADAPTER_MISMATCHES = 4096                                   # ... the probes of both tolerate mismatches (the rate in FindOptsAdaptersMm)
 READ_STATS, READ_DUPLICATION = 1, 2                            # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
@@ -54,6 +55,11 @@ class FindOpts(C.Structure):
 class FindOptsAdapters(C.Structure):
     """kvq_find_opts_adapters: the 20 bytes of kvq_find_opts, then the probes of FIND_ADAPTERS"""
     _fields_ = [('base', FindOpts), ('n_probes', C.c_int32), ('lens', C.c_uint8 * 8), ('probes', (C.c_uint8 * 32) * 8)]
+
+
+class FindOptsAdaptersMm(C.Structure):
+    """kvq_find_opts_adapters_mm: kvq_find_opts_adapters, then the mismatch rate of FIND_ADAPTER_MISMATCHES"""
+    _fields_ = [('a', FindOptsAdapters), ('mismatch_per', C.c_int32)]
 
 
 class GzipReport(C.Structure):
@@ -155,6 +161,10 @@ PROTOTYPES = {
     'kvq_scan_clip': (P(i64), [vp]),
     'kvq_clip_host': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, P(i64)]),
     'kvq_scan_clip_kernel_ms': (C.c_double, [vp]),
+    'kvq_scan_set_adapter_mismatches': (i32, [vp, i32]),
+    'kvq_scan_adapter_mismatches': (i32, [vp]),
+    'kvq_adapt_host_mm': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, i32, P(i64)]),
+    'kvq_clip_host_mm': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, i32, P(i64)]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

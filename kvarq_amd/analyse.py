@@ -74,7 +74,7 @@ class Analyser(object):
         (``info['profile']['cycles']``), ``per_read=True`` / ``duplication=True`` the per-read distributions / the
         duplication (``info['profile']['per_read']`` / ``['duplication']``), ``overrepresented=True`` the overrepresented
         sequences (``info['profile']['overrepresented']``), ``adapters=`` the adapter content (``info['profile']['adapters']``); ``clip=`` masks the
-        scores of adapters ahead of the trim and keeps what it did in ``self.clip``; ``long_reads``: as for ``engine.findseqs``,
+        scores of adapters ahead of the trim and keeps what it did in ``self.clip``; ``adapter_mismatches=`` lets the probes of both tolerate mismatches; ``long_reads``: as for ``engine.findseqs``,
         which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()

@@ -206,6 +206,17 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         nprobes = oa->n_probes;
         for (int32_t k = 0; k < nprobes; k++) { probes[k] = oa->probes[k]; probe_lens[k] = oa->lens[k]; }
     }
+    // the mismatch rate of KVQ_FIND_ADAPTER_MISMATCHES rides behind the probes: read only with the flag, and only when the size covers it
+    int32_t mismatch_per = 0;
+    if (flags & KVQ_FIND_ADAPTER_MISMATCHES) {
+        if (!(flags & (KVQ_FIND_ADAPTERS | KVQ_FIND_CLIP))) {
+            kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_ADAPTER_MISMATCHES needs KVQ_FIND_ADAPTERS or KVQ_FIND_CLIP (it is the rule of their probes)");
+            return nullptr;
+        }
+        if (opts->size < sizeof(kvq_find_opts_adapters_mm)) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: bad size"); return nullptr; }
+        mismatch_per = ((const kvq_find_opts_adapters_mm *)opts)->mismatch_per;
+        if (!adapt_per_ok("kvq_findseqs_opts", mismatch_per)) return nullptr;
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -245,7 +256,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
               kvq_scan_set_read_stats(s, ((flags & KVQ_FIND_READ_STATS) ? KVQ_READ_STATS : 0) | ((flags & KVQ_FIND_DUPLICATION) ? KVQ_READ_DUPLICATION : 0)) ||
               kvq_scan_set_overrepresented(s, (flags & KVQ_FIND_OVERREPRESENTED) ? 1 : 0) ||
               kvq_scan_set_adapters(s, probes, probe_lens, (flags & KVQ_FIND_ADAPTERS) ? nprobes : 0) ||
-              kvq_scan_set_clip(s, probes, probe_lens, (flags & KVQ_FIND_CLIP) ? nprobes : 0))) {
+              kvq_scan_set_clip(s, probes, probe_lens, (flags & KVQ_FIND_CLIP) ? nprobes : 0) ||
+              kvq_scan_set_adapter_mismatches(s, mismatch_per))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
     }
     const double tf1 = now_ms();

@@ -253,6 +253,8 @@ struct kvq_scan {
     int32_t adapt_n = 0; uint8_t adapt_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t adapt_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
     // the adapter clip (kvq_scan_set_clip): its probes (clip_n == 0: off); its array is passes[KVQ_PASS_CLIP]
     int32_t clip_n = 0; uint8_t clip_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t clip_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
+    // one mismatch per this many bases in the probes of both (kvq_scan_set_adapter_mismatches): 0, the exact rule, or 10 .. 32
+    int32_t adapt_per = 0;
 };
 
 // kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal

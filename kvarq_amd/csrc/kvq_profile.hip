@@ -1,5 +1,5 @@
 // kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16, 17 and 18), host side: the profile, the
-// per-cycle counts, the per-read statistics, the overrepresented sequences, the adapter content and the adapter clip (section 19) as options of a scan object, the steps of their common lifecycle, the launch of
+// per-cycle counts, the per-read statistics, the overrepresented sequences, the adapter content and the adapter clip (section 19), with the mismatch rate of their probes (section 20), as options of a scan object, the steps of their common lifecycle, the launch of
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
 #include <array>
@@ -144,9 +144,14 @@ static void passes_landed(kvq_scan *s)
         // the words that are no sums: n and every m_k
         std::vector<int64_t> &h = s->passes[KVQ_PASS_ADAPT].h;
         h[KVQ_ADAPT_N] = s->adapt_n;
+        if (s->adapt_per) h[KVQ_ADAPT_PER] = s->adapt_per;
         for (int k = 0; k < s->adapt_n; k++) h[KVQ_ADAPT_BLOCKS + (size_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = s->adapt_lens[k];
     }
-    if (s->passes[KVQ_PASS_CLIP].on) s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_N] = s->clip_n;      // (the word that is no sum)
+    if (s->passes[KVQ_PASS_CLIP].on) {
+        // the words that are no sums: n and per
+        s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_N] = s->clip_n;
+        if (s->adapt_per) s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_PER] = s->adapt_per;
+    }
 }
 // what an accessor hands out: the copy of a pass that is on, of a finished scan
 static const int64_t *pass_result(const kvq_scan *s, int which)
@@ -396,12 +401,47 @@ static KvqAdaptProbes adapt_probes(int32_t n, const uint8_t *lens, const uint8_t
     return P;
 }
 
-// the pass over the R records of a batch, behind its other passes: the probes go along by value, as 2-bit codes
+// ---- probes that tolerate mismatches ----
+extern "C" int32_t kvq_scan_set_adapter_mismatches(kvq_scan *s, int32_t per)
+{
+    int rc;
+    kvq_clear_error();
+    if ((rc = scan_idle(s, "kvq_scan_set_adapter_mismatches"))) return rc;
+    if (!adapt_per_ok("kvq_scan_set_adapter_mismatches", per)) return KVQ_ERR_RUNTIME;
+    s->adapt_per = per;
+    return KVQ_OK;
+}
+extern "C" int32_t kvq_scan_adapter_mismatches(const kvq_scan *s) { return s->adapt_per; }
+
+// n probes as the tolerant kernels take them, by value: two planes of one bit a base, masks, lengths and budgets
+// (kvq_adapt_records_mm and kvq_clip_records_mm)
+static KvqAdaptProbesMm adapt_probes_mm(int32_t n, const uint8_t *lens, const uint8_t (*probes)[KVQ_ADAPT_MAX_PROBE], int32_t per)
+{
+    KvqAdaptProbesMm P; memset(&P, 0, sizeof(P));
+    P.n = (uint32_t)n; P.per = (uint32_t)per;
+    for (int k = 0; k < n; k++) {
+        const uint32_t m = lens[k];
+        for (uint32_t i = 0; i < m; i++) { P.lo[k] |= (uint32_t)((probes[k][i] >> 1) & 1u) << i; P.hi[k] |= (uint32_t)((probes[k][i] >> 2) & 1u) << i; }
+        P.mask[k] = m >= 32u ? ~0u : (1u << m) - 1u;                            // (no shift by 32)
+        P.m[k] = m; P.e[k] = m / (uint32_t)per;
+    }
+    return P;
+}
+
+// the pass over the R records of a batch, behind its other passes: the probes go along by value, as 2-bit codes; with a mismatch
+// rate, the tolerant kernel in place of the exact one
 static int adapt_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
 {
     if (R == 0) return KVQ_OK;
-    const KvqAdaptProbes P = adapt_probes(s->adapt_n, s->adapt_lens, s->adapt_probes);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
+    if (s->adapt_per > 0) {
+        const KvqAdaptProbesMm P = adapt_probes_mm(s->adapt_n, s->adapt_lens, s->adapt_probes, s->adapt_per);
+        hipLaunchKernelGGL(kvq_adapt_mm_kernel(P.n), dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
+                           (uint32_t)R, P, s->passes[KVQ_PASS_ADAPT].d.as<unsigned long long>());
+        KVQ_HIP(hipGetLastError());
+        return KVQ_OK;
+    }
+    const KvqAdaptProbes P = adapt_probes(s->adapt_n, s->adapt_lens, s->adapt_probes);
     hipLaunchKernelGGL(kvq_adapt_kernel(P.n), dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
                        (uint32_t)R, P, s->passes[KVQ_PASS_ADAPT].d.as<unsigned long long>());
     KVQ_HIP(hipGetLastError());
@@ -443,8 +483,15 @@ extern "C" int32_t kvq_scan_set_clip(kvq_scan *s, const uint8_t *const *probes, 
 static int clip_enqueue(kvq_scan *s, uint8_t *d_data, uint64_t R)
 {
     if (R == 0) return KVQ_OK;
-    const KvqAdaptProbes P = adapt_probes(s->clip_n, s->clip_lens, s->clip_probes);
     const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
+    if (s->adapt_per > 0) {
+        const KvqAdaptProbesMm P = adapt_probes_mm(s->clip_n, s->clip_lens, s->clip_probes, s->adapt_per);
+        hipLaunchKernelGGL(kvq_clip_mm_kernel(P.n), dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, P,
+                           s->passes[KVQ_PASS_CLIP].d.as<unsigned long long>());
+        KVQ_HIP(hipGetLastError());
+        return KVQ_OK;
+    }
+    const KvqAdaptProbes P = adapt_probes(s->clip_n, s->clip_lens, s->clip_probes);
     hipLaunchKernelGGL(kvq_clip_kernel(P.n), dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, P,
                        s->passes[KVQ_PASS_CLIP].d.as<unsigned long long>());
     KVQ_HIP(hipGetLastError());

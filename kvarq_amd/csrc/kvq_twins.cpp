@@ -1,7 +1,7 @@
 // kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes and of the adapter clip (include/kvarq_hip.h, DESIGN sections 13,
-// 14, 16, 17, 18 and 19): the definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records, kvq_over_records,
-// kvq_adapt_records and kvq_clip_records in plain C++ (test infrastructure, never a fallback).  Nothing of HIP: the file also
-// compiles on its own.  One argument check and one record walk serve all six.
+// 14, 16, 17, 18, 19 and 20): the definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records, kvq_over_records,
+// kvq_adapt_records, kvq_clip_records, kvq_adapt_records_mm and kvq_clip_records_mm in plain C++ (test infrastructure, never a
+// fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record walk serve all eight.
 #include "../../include/kvarq_hip.h"
 #include "kvq_dup_hash.h"
 #include <algorithm>
@@ -226,6 +226,95 @@ extern "C" int32_t kvq_clip_host(uint8_t *text, int64_t nbytes, const int64_t *c
             for (int64_t p = 0; first < 0 && p + m <= L; p++) if (!memcmp(line + p, probes[k], (size_t)m)) first = p;
             for (int64_t t = std::min(m - 1, L); first < 0 && tail < 0 && t >= KVQ_ADAPT_MIN_TAIL; t--)
                 if (!memcmp(line + L - t, probes[k], (size_t)t)) tail = t;
+            if (first >= 0) clip = std::min(clip, first);
+            else if (tail >= 0) clip = std::min(clip, L - tail);
+        }
+        out[KVQ_CLIP_RECORDS]++;
+        if (clip >= L) return;
+        out[KVQ_CLIP_CLIPPED]++; out[KVQ_CLIP_MASKED] += std::max<int64_t>(0, S - clip); out[KVQ_CLIP_BASES_CUT] += L - clip;
+        for (int64_t p = clip; p < S; p++) text[n2 + 1 + p] = '!';
+    });
+    return KVQ_OK;
+}
+
+// ---- probes that tolerate mismatches ----
+static bool adapt_per_ok(const char *who, int32_t per)
+{
+    const bool ok = per == 0 || (per >= KVQ_ADAPT_MIN_PER && per <= KVQ_ADAPT_MAX_PER);
+    if (!ok) kvq_set_error(KVQ_ERR_RUNTIME, "%s: the mismatch rate is 0 (exact) or one mismatch per %d to %d bases", who, KVQ_ADAPT_MIN_PER, KVQ_ADAPT_MAX_PER);
+    return ok;
+}
+// the positions at which a[0, n) and b[0, n) differ, as bytes
+static int64_t adapt_ham(const uint8_t *a, const uint8_t *b, int64_t n)
+{
+    int64_t d = 0;
+    for (int64_t i = 0; i < n; i++) d += a[i] != b[i];
+    return d;
+}
+// FIRST, DIST and TAIL of one probe of m bytes on a line of L bytes (-1: none); E(len) = len / per, 0 when per is 0
+static void adapt_search_mm(const uint8_t *line, int64_t L, const uint8_t *probe, int64_t m, int32_t per, int64_t &first, int64_t &dist, int64_t &tail)
+{
+    first = dist = tail = -1;
+    const int64_t Em = per ? m / per : 0;
+    for (int64_t p = 0; first < 0 && p + m <= L; p++) {                       // the smallest p, whatever a later window's distance
+        const int64_t d = adapt_ham(line + p, probe, m);
+        if (d <= Em) { first = p; dist = d; }
+    }
+    for (int64_t t = std::min(m - 1, L); first < 0 && tail < 0 && t >= KVQ_ADAPT_MIN_TAIL; t--)     // the largest t, E of t
+        if (adapt_ham(line + L - t, probe, t) <= (per ? t / per : 0)) tail = t;
+}
+
+extern "C" int32_t kvq_adapt_host_mm(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                     const uint8_t *const *probes, const int32_t *lens, int32_t n, int32_t per, int64_t *out)
+{
+    if (!twin_args("kvq_adapt_host_mm", out != nullptr, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    if (!adapt_probes_ok("kvq_adapt_host_mm", probes, lens, n) || !adapt_per_ok("kvq_adapt_host_mm", per)) return KVQ_ERR_RUNTIME;
+    out[KVQ_ADAPT_N] = n;
+    if (per) out[KVQ_ADAPT_PER] = per;
+    for (int32_t k = 0; k < n; k++) out[KVQ_ADAPT_BLOCKS + (int64_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = lens[k];
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t, int64_t) {
+        const uint8_t *line = text + n0 + 1;
+        int64_t L = n1 - n0 - 1;
+        if (L > 0 && line[L - 1] == '\r') L--;                                 // a trailing '\r' is not part of its line
+        int64_t clip = L;
+        bool full = false, tailed = false;
+        for (int32_t k = 0; k < n; k++) {
+            int64_t *const blk = out + KVQ_ADAPT_BLOCKS + (int64_t)k * KVQ_ADAPT_BLOCK_WORDS;
+            int64_t first, dist, tail;
+            adapt_search_mm(line, L, probes[k], lens[k], per, first, dist, tail);
+            if (first >= 0) {
+                full = true; clip = std::min(clip, first);
+                blk[KVQ_ADAPT_B_FIRST]++;
+                blk[first < KVQ_ADAPT_POSITIONS ? KVQ_ADAPT_B_FIRST_BINS + first : (int64_t)KVQ_ADAPT_B_BEYOND]++;
+                if (per) blk[KVQ_ADAPT_B_DIST + dist]++;
+            } else if (tail >= 0) {
+                tailed = true; clip = std::min(clip, L - tail);
+                blk[KVQ_ADAPT_B_TAIL]++; blk[KVQ_ADAPT_B_TAIL_BINS + tail]++;
+            }
+        }
+        out[KVQ_ADAPT_RECORDS]++;
+        out[full ? KVQ_ADAPT_WITH_FULL : KVQ_ADAPT_TAIL_ONLY] += full || tailed;
+        out[KVQ_ADAPT_CLIP + std::min<int64_t>(clip, KVQ_ADAPT_CLIP_BINS - 1)]++;
+    });
+    return KVQ_OK;
+}
+
+extern "C" int32_t kvq_clip_host_mm(uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
+                                    const uint8_t *const *probes, const int32_t *lens, int32_t n, int32_t per, int64_t *out)
+{
+    if (!twin_args("kvq_clip_host_mm", out != nullptr, nbytes, chunk_off, nchunks)) return KVQ_ERR_RUNTIME;
+    if (!adapt_probes_ok("kvq_clip_host_mm", probes, lens, n) || !adapt_per_ok("kvq_clip_host_mm", per)) return KVQ_ERR_RUNTIME;
+    out[KVQ_CLIP_N] = n;
+    if (per) out[KVQ_CLIP_PER] = per;
+    for_each_record(text, chunk_off, nchunks, [&](int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
+        const uint8_t *line = text + n0 + 1;
+        int64_t L = n1 - n0 - 1, S = n3 - n2 - 1;
+        if (L > 0 && line[L - 1] == '\r') L--;                                 // a trailing '\r' is not part of its line
+        if (S > 0 && text[n2 + S] == '\r') S--;
+        int64_t clip = L;
+        for (int32_t k = 0; k < n; k++) {
+            int64_t first, dist, tail;
+            adapt_search_mm(line, L, probes[k], lens[k], per, first, dist, tail);
             if (first >= 0) clip = std::min(clip, first);
             else if (tail >= 0) clip = std::min(clip, L - tail);
         }

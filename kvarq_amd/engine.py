@@ -222,6 +222,13 @@ def findseqs(fname, sequences, *, inflate='host', **options):
     text.  The dict gains 'clip' (``profile.Clip``: ``records``, ``clipped``, ``masked``, ``bases_cut``,
     ``words``) and 'clip_kernel_ms'.  It needs no profile; a configured Amin of '!' or below is refused.
 
+    adapter_mismatches=True / 10 .. 32 (with ``adapters`` or ``clip``): the probes of both
+    tolerate substitutions -- a comparison over ``len`` bases may differ from the probe in ``len // per``
+    positions, True meaning per = 10 (one mismatch in a 12-base probe, none in a tail shorter than 10).  An
+    'N', a lower-case letter or any other byte is one mismatch.  The earliest window within the budget is
+    the adapter's first base; ``Adapters.first_mismatches`` tells how many of them differed in 0 .. 3 places.
+    None, False or 0: the probes match byte for byte, as without the option.
+
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
     no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are

@@ -1,11 +1,28 @@
 """
 The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
-``duplication``, ``overrepresented``, ``adapters``, ``clip`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+``duplication``, ``overrepresented``, ``adapters``, ``clip``, ``adapter_mismatches`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
 everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
 """
 import ctypes as C
+import operator
 
 from . import _lib
+
+
+def as_mismatch_per(adapter_mismatches):
+    """the ``per`` of kvq_scan_set_adapter_mismatches for an ``adapter_mismatches`` option: None, False or 0 -> 0 (exact), True -> 10,
+    an int 10 .. 32 -> itself"""
+    if adapter_mismatches is None or adapter_mismatches is False:
+        return 0
+    if adapter_mismatches is True:
+        return 10
+    try:
+        per = operator.index(adapter_mismatches)             # (any integer type, numpy's among them; no float, no string)
+    except TypeError:
+        per = -1
+    if not (per == 0 or 10 <= per <= 32):
+        raise ValueError('adapter_mismatches is None, False or 0 (exact), True (10) or an int 10 .. 32: one mismatch per that many bases')
+    return per
 
 
 class ScanOptions(object):
@@ -18,10 +35,12 @@ class ScanOptions(object):
     ``cycles``, ``per_read``, ``duplication``, ``overrepresented`` or ``adapters`` without ``profile`` mean a profile with no cutoffs.
     ``clip``: the probes of the adapter clip ahead of the trim, in the forms of ``adapters`` -- ``clip_names`` and
     ``clip``, a list of bytes, here; it needs no profile.  ``adapters`` and ``clip`` together must name the same probes (``findseqs``
-    has one probe block): otherwise ValueError."""
+    has one probe block): otherwise ValueError.  ``adapter_mismatches``: the probes of both tolerate one mismatch per that many bases
+     -- None, False or 0: exact; True: 10; an int 10 .. 32 as given -- ``mismatch_per``, an int, here; without
+    ``adapters`` or ``clip``, and outside the range: ValueError."""
 
     def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, overrepresented=False,
-                 adapters=None, clip=None, amin=None):
+                 adapters=None, clip=None, amin=None, adapter_mismatches=None):
         self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
         self.records, self.cycles, self.overrepresented = bool(records), bool(cycles), bool(overrepresented)
         self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
@@ -39,6 +58,9 @@ class ScanOptions(object):
             a = None if amin is None else amin & 0xFF if isinstance(amin, int) else (amin.encode('latin-1') if isinstance(amin, str) else bytes(amin))[0]
             if a is not None and (a ^ 0x80) - 0x80 <= ord('!'):
                 raise ValueError("clip= needs an Amin above '!': a masked score would end no run")
+        self.mismatch_per = as_mismatch_per(adapter_mismatches)
+        if self.mismatch_per and not (self.adapters or self.clip):
+            raise ValueError('adapter_mismatches= is the rule of the probes of adapters= or clip=: give one of them')
         if (self.cycles or self.read_stats or self.overrepresented or self.adapters) and profile is None:
             profile = ()
         self.profile = None
@@ -62,7 +84,11 @@ class ScanOptions(object):
         o = _lib.FindOptsAdapters(base, len(probes), (C.c_uint8 * 8)(*[len(p) for p in probes]))
         for k, p in enumerate(probes):
             C.memmove(o.probes[k], p, len(p))
-        return o
+        if not self.mismatch_per:
+            return o
+        # (the rate rides behind the probes, which stay what they are whenever it is off)
+        o.base.size, o.base.flags = C.sizeof(_lib.FindOptsAdaptersMm), o.base.flags | _lib.FIND_ADAPTER_MISMATCHES
+        return _lib.FindOptsAdaptersMm(o, self.mismatch_per)
 
     def setters(self):
         """the kvq_scan_set_* calls of a new scan handle, in order: (name, arguments behind the handle)"""
@@ -81,6 +107,8 @@ class ScanOptions(object):
         if self.clip:
             n = len(self.clip)
             calls.append(('kvq_scan_set_clip', ((C.c_char_p * n)(*self.clip), (C.c_int32 * n)(*[len(p) for p in self.clip]), n)))
+        if self.mismatch_per:
+            calls.append(('kvq_scan_set_adapter_mismatches', (self.mismatch_per,)))
         if self.long_mode:
             calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
         return calls

@@ -67,6 +67,7 @@ ADAPT_B_M, ADAPT_B_FIRST, ADAPT_B_BEYOND, ADAPT_B_TAIL, ADAPT_B_FIRST_BINS, ADAP
 ADAPT_MAX_PROBES, ADAPT_MIN_PROBE, ADAPT_MAX_PROBE, ADAPT_MIN_TAIL, ADAPT_POSITIONS = 8, 8, 32, 6, 1024
 ADAPT_CLIP, ADAPT_CLIP_BINS = ADAPT_BLOCKS + ADAPT_MAX_PROBES * ADAPT_BLOCK_WORDS, 1025
 ADAPT_LEN = ADAPT_CLIP + ADAPT_CLIP_BINS
+ADAPT_PER, ADAPT_B_DIST = 4, 4                                     # (written only with adapter_mismatches: DESIGN section 20)
 
 Overrepresented = collections.namedtuple('Overrepresented', 'sequence count share hash source')
 
@@ -135,7 +136,9 @@ class Adapters(object):
     (n): those where it starts at 1024 and further; ``tail`` (n x 32): the records without a full occurrence of probe k whose
     line ends with its first t bases (t >= 6, the longest such t); ``clip`` (1025): the records by the length an adapter clip
     would leave, 1024 and more in the last bin; ``records``, ``with_adapter`` (records with a full occurrence of any probe),
-    ``tail_only`` (records with none but a tail match); ``words``: the flat array"""
+    ``tail_only`` (records with none but a tail match); ``words``: the flat array.  ``mismatch_per``: 0 when the probes matched
+    byte for byte, else the ``per`` of ``adapter_mismatches``, and ``first_mismatches`` (n x 4): the records
+    whose first occurrence of probe k differs from it in 0, 1, 2, 3 positions (all zero with ``mismatch_per`` 0)"""
 
     def __init__(self, words, names=None, probes=None):
         self.words = w = np.array(words, dtype=np.int64)
@@ -151,6 +154,8 @@ class Adapters(object):
         self.first = blocks[:, ADAPT_B_FIRST_BINS:ADAPT_B_FIRST_BINS + ADAPT_POSITIONS]
         self.tail = blocks[:, ADAPT_B_TAIL_BINS:ADAPT_B_TAIL_BINS + 32]
         self.clip = w[ADAPT_CLIP:ADAPT_CLIP + ADAPT_CLIP_BINS]
+        self.mismatch_per = int(w[ADAPT_PER])
+        self.first_mismatches = blocks[:, ADAPT_B_DIST:ADAPT_B_DIST + 4]
 
     def __eq__(self, other):
         return isinstance(other, Adapters) and bool((self.words == other.words).all())
@@ -161,10 +166,15 @@ class Adapters(object):
     def as_dict(self):
         def bins(h):
             return {int(b): int(h[b]) for b in np.nonzero(h)[0]}
-        return {'records': self.records, 'with_adapter': self.with_adapter, 'tail_only': self.tail_only, 'clip': bins(self.clip),
-                'probes': [{'name': self.names[k], 'sequence': self.probes[k].decode('latin-1') if self.probes[k] is not None else None,
-                            'length': self.lengths[k], 'found': int(self.found[k]), 'beyond': int(self.beyond[k]), 'tailed': int(self.tailed[k]),
-                            'first': bins(self.first[k]), 'tail': bins(self.tail[k])} for k in range(len(self.names))]}
+        d = {'records': self.records, 'with_adapter': self.with_adapter, 'tail_only': self.tail_only, 'clip': bins(self.clip),
+             'probes': [{'name': self.names[k], 'sequence': self.probes[k].decode('latin-1') if self.probes[k] is not None else None,
+                         'length': self.lengths[k], 'found': int(self.found[k]), 'beyond': int(self.beyond[k]), 'tailed': int(self.tailed[k]),
+                         'first': bins(self.first[k]), 'tail': bins(self.tail[k])} for k in range(len(self.names))]}
+        if self.mismatch_per:
+            d['mismatch_per'] = self.mismatch_per
+            for k, probe in enumerate(d['probes']):
+                probe['first_mismatches'] = [int(v) for v in self.first_mismatches[k]]
+        return d
 
 
 def profile_len(ncut):
@@ -592,6 +602,8 @@ class Profile(object):
             lines.append('%s %s: found=%d (%.4f) first cycle=%s beyond=%d tails=%d'
                          % (name, a.probes[k].decode('latin-1') if a.probes[k] is not None else '?', int(a.found[k]),
                             int(a.found[k]) / float(a.records) if a.records else 0.0, int(at[0]) if at.size else '-', int(a.beyond[k]), int(a.tailed[k])))
+            if a.mismatch_per:
+                lines[-1] += ' mismatches(1 per %d)=%s' % (a.mismatch_per, '/'.join(str(int(v)) for v in a.first_mismatches[k]))
         return lines
 
     def summary(self):
@@ -635,6 +647,7 @@ class Profile(object):
 
 
 CLIP_N, CLIP_RECORDS, CLIP_CLIPPED, CLIP_MASKED, CLIP_BASES_CUT, CLIP_LEN = 0, 1, 2, 3, 4, 8      # (include/kvarq_hip.h: kvq_clip_len())
+CLIP_PER = 5                                                       # (written only with adapter_mismatches)
 
 
 class Clip(object):
@@ -647,6 +660,7 @@ class Clip(object):
         assert w.shape == (CLIP_LEN,)
         self.records, self.clipped, self.masked, self.bases_cut = int(w[CLIP_RECORDS]), int(w[CLIP_CLIPPED]), int(w[CLIP_MASKED]), int(w[CLIP_BASES_CUT])
         self.names, self.probes = names, probes
+        self.mismatch_per = int(w[CLIP_PER])    # 0: the probes matched byte for byte; else the ``per`` of ``adapter_mismatches``
 
     def __eq__(self, other):
         return isinstance(other, Clip) and np.array_equal(self.words, other.words)
@@ -661,7 +675,8 @@ class Clip(object):
 
     def line(self):
         return 'clip: records=%d clipped=%d (%.4f) masked=%d bases_cut=%d' % (
-            self.records, self.clipped, self.clipped / float(self.records) if self.records else float('nan'), self.masked, self.bases_cut)
+            self.records, self.clipped, self.clipped / float(self.records) if self.records else float('nan'), self.masked, self.bases_cut) + (
+            ' mismatches=1 per %d' % self.mismatch_per if self.mismatch_per else '')
 
 
 def clip_from_scan(L, h, clip=None):
@@ -671,17 +686,21 @@ def clip_from_scan(L, h, clip=None):
     return Clip(np.ctypeslib.as_array(ptr, shape=(CLIP_LEN,)).copy(), names, probes) if ptr else None
 
 
-def clip_host(text, clip, chunk_off=None, into=None):
-    """the CPU twin of the adapter clip (kvq_clip_host) over a text in host memory: (MASK(text) as a new uint8 array, the eight
-    words); ``into``: words to add to, as the twin does"""
+def clip_host(text, clip, chunk_off=None, into=None, adapter_mismatches=None):
+    """the CPU twin of the adapter clip (kvq_clip_host; with ``adapter_mismatches``: kvq_clip_host_mm) over a text in host memory:
+    (MASK(text) as a new uint8 array, the eight words); ``into``: words to add to, as the twin does"""
     from . import scan
+    from .options import as_mismatch_per
     _, probes = as_adapters(clip)
+    per = as_mismatch_per(adapter_mismatches)
     arr = (np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)).copy()
     co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
     n = len(probes)
     words = np.zeros(CLIP_LEN, dtype=np.int64) if into is None else into
-    if _lib.lib().kvq_clip_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
-                                (C.c_char_p * n)(*probes), (C.c_int32 * n)(*[len(p) for p in probes]), n, words.ctypes.data_as(C.POINTER(C.c_int64))):
+    args = (arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+            (C.c_char_p * n)(*probes), (C.c_int32 * n)(*[len(p) for p in probes]), n)
+    out = words.ctypes.data_as(C.POINTER(C.c_int64))
+    if _lib.lib().kvq_clip_host_mm(*(args + (per, out))) if per else _lib.lib().kvq_clip_host(*(args + (out,))):
         raise RuntimeError(_lib.last_error()[1])
     return arr, words
 
@@ -706,18 +725,22 @@ def from_scan(L, h, sources=None, adapters=None):
 
 
 def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False, duplication=False, slots=0, overrepresented=False,
-                 over_records=0, sources=None, adapters=None, clip=None):
+                 over_records=0, sources=None, adapters=None, clip=None, adapter_mismatches=None):
     """the CPU twin (kvq_profile_host; cycles: and kvq_cycles_host; per_read / duplication: and kvq_reads_host, with a
     table of ``slots`` slots, 0: the default; overrepresented: and kvq_over_host, with the first ``over_records`` records
     making the candidates, 0: the default; adapters: and kvq_adapt_host, with the probes of ``as_adapters``) over a text in host memory; chunk_off None: the reader's chunk cuts;
-    clip: the profile of a copy of the text that kvq_clip_host has masked with these probes (``Profile.clipped``: the ``Clip``)"""
+    clip: the profile of a copy of the text that kvq_clip_host has masked with these probes (``Profile.clipped``: the ``Clip``);
+    adapter_mismatches: the probes of both tolerate mismatches (kvq_adapt_host_mm, kvq_clip_host_mm; as for ``ScanOptions``)"""
     from . import scan
+    from .options import as_mismatch_per
+    if as_mismatch_per(adapter_mismatches) and adapters in (None, False) and clip in (None, False):
+        raise ValueError('adapter_mismatches= is the rule of the probes of adapters= or clip=: give one of them')
     cuts = as_cutoffs(cutoffs)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
     co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
     clipped = None
     if clip is not None and clip is not False:
-        arr, words = clip_host(arr, clip, co)
+        arr, words = clip_host(arr, clip, co, adapter_mismatches=adapter_mismatches)
         clipped = Clip(words, *as_adapters(clip))
     out = np.zeros(profile_len(len(cuts)), dtype=np.int64)
     rc = _lib.lib().kvq_profile_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -745,22 +768,27 @@ def profile_host(text, cutoffs=(), chunk_off=None, cycles=False, per_read=False,
             raise RuntimeError(_lib.last_error()[1])
     ada = None
     if adapters is not None and adapters is not False:
-        ada = adapt_host(arr, adapters, co)
+        ada = adapt_host(arr, adapters, co, adapter_mismatches=adapter_mismatches)
     p = Profile(out, cuts, cyc, reads, dup, over, sources, ada)
     p.clipped = clipped
     return p
 
 
-def adapt_host(text, adapters, chunk_off=None):
-    """the CPU twin of the adapter content alone (kvq_adapt_host) over a text in host memory: an ``Adapters``"""
+def adapt_host(text, adapters, chunk_off=None, adapter_mismatches=None):
+    """the CPU twin of the adapter content alone (kvq_adapt_host; with ``adapter_mismatches``: kvq_adapt_host_mm) over a text in
+    host memory: an ``Adapters``"""
     from . import scan
+    from .options import as_mismatch_per
     names, probes = as_adapters(adapters)
+    per = as_mismatch_per(adapter_mismatches)
     arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
     co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
     n = len(probes)
     words = np.zeros(ADAPT_LEN, dtype=np.int64)
-    if _lib.lib().kvq_adapt_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
-                                 (C.c_char_p * n)(*probes), (C.c_int32 * n)(*[len(p) for p in probes]), n, words.ctypes.data_as(C.POINTER(C.c_int64))):
+    args = (arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+            (C.c_char_p * n)(*probes), (C.c_int32 * n)(*[len(p) for p in probes]), n)
+    out = words.ctypes.data_as(C.POINTER(C.c_int64))
+    if _lib.lib().kvq_adapt_host_mm(*(args + (per, out))) if per else _lib.lib().kvq_adapt_host(*(args + (out,))):
         raise RuntimeError(_lib.last_error()[1])
     return Adapters(words, names, probes)
 
@@ -770,7 +798,8 @@ def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     per-cycle counts; ``per_read`` / ``duplication``: with the per-read distributions / the duplication; ``overrepresented``:
     with the overrepresented sequences, labelled from ``sources`` (None: ``KNOWN_SOURCES``); ``adapters``: with the adapter
     content of these probes (``as_adapters``); ``clip``: of the input with the scores of its adapters masked (DESIGN section 19;
-    ``Profile.clipped``: the ``Clip``); ``long_reads``: as for
+    ``Profile.clipped``: the ``Clip``); ``adapter_mismatches``: the probes of both tolerate mismatches (DESIGN section 20);
+    ``long_reads``: as for
     ``engine.findseqs``, which takes the ``options``"""
     from . import engine
     r = engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)
@@ -795,7 +824,13 @@ def main(argv=None):
     ap.add_argument('--overrepresented', action='store_true', help='the sequences (first 64 bases) that make up 0.1 %% of the reads and more, among those of the first 2^18 records: count, share, known source')
     ap.add_argument('--adapters', nargs='*', metavar='NAME=SEQ', help='the adapter content: how many reads hold each probe and from which cycle on, tails of 6 bases and more, the length a clip would leave; without arguments: the known adapters')
     ap.add_argument('--clip', nargs='*', metavar='NAME=SEQ', help="the profile of the input with the scores of its adapters set to '!' ahead of the trim, and how much was clipped; without arguments: the known adapters (with --adapters: the same probes)")
+    ap.add_argument('--adapter-mismatches', nargs='?', type=int, const=10, default=None, metavar='PER',
+                    help='with --adapters or --clip: the probes tolerate one mismatch per PER bases (10 .. 32; without a value: 10); the adapter lines gain the counts of first occurrences with 0/1/2/3 mismatches')
     a = ap.parse_args(argv)
+    if a.adapter_mismatches is not None and a.adapters is None and a.clip is None:
+        ap.error('--adapter-mismatches needs --adapters or --clip')
+    if a.adapter_mismatches is not None and not 10 <= a.adapter_mismatches <= 32:
+        ap.error('--adapter-mismatches takes 10 .. 32')
     more = dict(cycles=a.cycles, per_read=a.per_read, duplication=a.duplication, overrepresented=a.overrepresented)
     if a.adapters is not None:
         for item in a.adapters:
@@ -807,6 +842,8 @@ def main(argv=None):
             if '=' not in item:
                 ap.error('--clip takes NAME=SEQ')
         more['clip'] = collections.OrderedDict((i.split('=', 1)[0], i.split('=', 1)[1].encode('latin-1')) for i in a.clip) if a.clip else True
+    if a.adapter_mismatches is not None:
+        more['adapter_mismatches'] = a.adapter_mismatches
     p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
