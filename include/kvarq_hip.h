@@ -525,6 +525,25 @@ void    kvq_scan_order_info(const kvq_scan *s, int64_t out[9]);
  * out[0], out[2], out[3] are zero until the scan is finished and when it had no seed-filter launch.  The words are read
  * from the device when this is called; a scan that does not call it does nothing for it.  Returns 0 or an error code. */
 int32_t kvq_scan_match_info(const kvq_scan *s, int64_t out[4]);
+/* (measurement) what the host decided for the seed-filter launches of this scan object since kvq_scan_create / kvq_scan_reset
+ * (a replay of device batches after a hit-arena overflow launches again and is counted again):
+ *   out[0] launches   seed-filter launches (a batch without a tile launches nothing and is not counted)
+ *   out[1] pipelined  ... that found the scan kernel in front of them, another scan object's, still on the device
+ *   out[2] beside     ... that published the chain AHEAD of their kvq_verify_survivors: the next scan of the process runs
+ *                     beside this one's survivors, validation, redo, fold, record gathering, input passes and finish tail.
+ *                     Equal to out[1] unless KVQ_SV_MODE is set (read once per process: 0 never beside, 1 always)
+ * and of the last of them:
+ *   out[3], out[4]    workgroups and threads of its kvq_verify_survivors: 256 x 1024 behind the scan, KVQ_SV_GRID (read once
+ *                     per process; 64) x 256 beside the next; a round of that kernel covers out[3] * out[4] slots of the list
+ *                     (both 0: the scan object has no list)
+ *   out[5] grid cap   the most workgroups its scan kernel might take (kvq_scan_grid: what it took)
+ *   out[6] ... and which: 1 every slot (four a CU), 2 one slot in four CUs left free (another scan object's kernel was on the
+ *                     device), 3 KVQ_GRID
+ *   out[7] CUs of the device      out[8] scan objects alive in the process at that moment
+ *   out[9] 1 when the last launch went beside
+ * All zero while there was no such launch.  Host-side facts only: it does no device work, and it steers nothing.  The tests
+ * assert with it that a scan took the order and the grid it was built for before they compare its result. */
+void    kvq_scan_launch_info(const kvq_scan *s, int64_t out[10]);
 /* (measurement) the exact record index of one batch in device memory, as every scan makes it for the exhaustive kernels, the
  * read-list route, the clip and the input passes -- the same checks, chunk table and kernels, on the scan's stream --, brought to
  * the host: chunk_nrec_out[c] the complete records of chunk c (nchunks words), and of the first min(R, cap) records

@@ -172,6 +172,7 @@ PROTOTYPES = {
     'kvq_scan_gap_ms': (C.c_double, [vp, vp]),
     'kvq_scan_order_info': (None, [vp, P(i64)]),
     'kvq_scan_match_info': (i32, [vp, P(i64)]),
+    'kvq_scan_launch_info': (None, [vp, P(i64)]),
     'kvq_scan_index_device': (i64, [vp, vp, i64, P(i64), i64, vp, vp, i64, vp]),
     'kvq_scan_set_keep_skipped': (i32, [vp, i32]),
     'kvq_scan_skipped_tiles': (i64, [vp, vp, i64]),

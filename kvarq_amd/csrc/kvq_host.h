@@ -187,6 +187,7 @@ struct kvq_scan {
     int path_bits = 0;
     int32_t kernel_cell = 0;           // the kvq_scan_bp instantiation of the last seed-filter launch (kvq_scan_kernel_pick)
     int32_t kernel_grid = 0;           // ... and its workgroups (kvq_scan_grid)
+    int64_t launch_info[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };         // kvq_scan_launch_info: the seed-filter launches since the scan was made or reset (kvq_launch.hip writes, nothing reads)
     std::vector<int64_t> cur_chunk_off;  // chunk offsets of the batch being enqueued
     size_t cur_co_at = 0;                // ... and where run_batch put them in the pool
     size_t cur_skip_at = 0, cur_first_at = 0; uint32_t cur_ntiles = 0;   // the batch's list of skipped tiles, its first-tile table
@@ -204,7 +205,7 @@ struct kvq_scan {
     std::vector<Batch> batches;
     bool host_batches = false;
     int64_t host_pending = -1;           // index of the host batch in flight (kvq_scan_host_async), -1: none
-    hipEvent_t ev_chain = nullptr;       // this scan's last seed-filter launch and its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles: what the next scan of the process waits for)
+    hipEvent_t ev_chain = nullptr;       // what the next scan of the process waits for.  One job at a time: this scan's last seed-filter launch AND its kvq_verify_survivors are through (recorded behind the two, in front of kvq_validate_tiles).  Jobs in flight (the launch went `beside`, kvq_seeded_launch): the scan kernel alone is through -- recorded behind it and IN FRONT of kvq_verify_survivors, which then runs beside the next scan
     int64_t parsed = 0, total = 0;
     // timing
     std::vector<KvqEventPair> ev_all, ev_main, ev_free;     // ev_free: pairs of earlier scans, reused (the passes below have their own)

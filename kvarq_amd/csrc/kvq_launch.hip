@@ -43,6 +43,8 @@ extern "C" int32_t kvq_scan_kernel_pick(int32_t k, int32_t stride, int32_t dense
 
 extern "C" int32_t kvq_scan_kernel(const kvq_scan *s) { return s->kernel_cell; }
 extern "C" int32_t kvq_scan_grid(const kvq_scan *s) { return s->kernel_grid; }
+// (measurement) what kvq_seeded_launch decided on the host for this scan's seed-filter launches: no device work, nothing steered
+extern "C" void kvq_scan_launch_info(const kvq_scan *s, int64_t out[10]) { for (int i = 0; i < 10; i++) out[i] = s->launch_info[i]; }
 
 int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, int64_t nbytes,
                       const uint32_t *d_chunk_off, int64_t nchunks, int64_t fpos_base, uint32_t max_chunk_bytes)
@@ -85,7 +87,9 @@ int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, in
     const uint32_t grid_full = cus * per_cu, grid_shared = grid_full - cus / 4u;
     // (round 4: ... and only while another scan of the process is actually on the device as this one is enqueued -- jobs in flight.  A caller
     // that runs its jobs one at a time gets every slot: the free ones bought it nothing, the scan alone is 2 % faster with all of them)
-    const uint32_t grid_cap = grid_env ? grid_env : (kvq_live_scans() > 1 && kvq_chain_busy(s)) ? grid_shared : grid_full;
+    const int live = kvq_live_scans();
+    const bool shared = !grid_env && live > 1 && kvq_chain_busy(s);
+    const uint32_t grid_cap = grid_env ? grid_env : shared ? grid_shared : grid_full;
     if (s->pool.used + ((size_t)nchunks + 1) * 4 + (size_t)nt * 24 + 24576 + KVQ_SKIP_CAP * sizeof(KvqSkippedTile) > s->pool.cap) {       // run_batch made the room
         kvq_set_error(KVQ_ERR_RUNTIME, "batch tables outgrew their reservation"); return KVQ_ERR_RUNTIME;
     }
@@ -185,6 +189,13 @@ int kvq_seeded_launch(kvq_scan *s, const KvqParams &P, const uint8_t *d_data, in
         hipLaunchKernelGGL(kvq_verify_survivors, dim3(beside ? sv_grid : 256), dim3(beside ? 256 : 1024), 0, s->stream, P, d_data, fpos_base, (const void *)s->d_surv.p,
                            (const unsigned int *)s->cur_fail, ix->k, ix->stride, ix->pitch);
     if (!beside) { const int rcp = kvq_chain_publish(s); if (rcp) return rcp; }            // (kvq_validate_tiles and what follows run beside the next scan)
+    {
+        // kvq_scan_launch_info: what was decided above, written down
+        int64_t *li = s->launch_info;
+        li[0]++; li[1] += pipelined ? 1 : 0; li[2] += beside ? 1 : 0;
+        li[3] = s->d_surv.p ? (beside ? sv_grid : 256) : 0; li[4] = s->d_surv.p ? (beside ? 256 : 1024) : 0;
+        li[5] = grid_cap; li[6] = grid_env ? 3 : shared ? 2 : 1; li[7] = cus; li[8] = live; li[9] = beside ? 1 : 0;
+    }
     if (!(dbg & 64u))          // (diagnostic 64 scans the wrong text on purpose: nothing to validate)
     hipLaunchKernelGGL(kvq_validate_tiles, dim3((uint32_t)((nchunks + 255) / 256)), dim3(256), 0, s->stream, (uint32_t)nchunks,
                        d_first, d_report, s->cur_fail, reinterpret_cast<KvqSkippedTile *>(s->pool.d + skip_at), d_chunk_off, TILE);

@@ -295,6 +295,7 @@ extern "C" int32_t kvq_scan_reset(kvq_scan *s)
     s->batches.clear(); s->host_batches = false; s->host_pending = -1; s->copied_pending = false; s->parsed = 0; s->total = 0;
     s->ms_all = s->ms_main = 0; for (KvqPass &p : s->passes) p.ms = 0;
     s->main_launches = 0; s->finished = false; s->reduced = false; s->gathered = false; s->path_bits = 0; s->kernel_cell = 0; s->kernel_grid = 0; s->n_hits = 0;
+    for (int64_t &w : s->launch_info) w = 0;
     s->tail_pending = false;
     s->kept_tiles.clear(); s->kept_redo.clear();
     s->pool.used = 0;

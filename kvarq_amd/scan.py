@@ -241,6 +241,21 @@ class Scanner(object):
         _check(_lib.lib().kvq_scan_match_info(self.h, out))
         return dict(zip(self.MATCH_INFO, (int(x) for x in out)))
 
+    LAUNCH_INFO = ('launches', 'pipelined', 'beside', 'sv_grid', 'sv_block', 'grid_cap', 'grid_cap_kind', 'cus', 'live_scans', 'last_beside')
+    GRID_CAP_KINDS = (None, 'grid_full', 'grid_shared', 'KVQ_GRID')
+
+    def launch_info(self):
+        """(measurement) ``kvq_scan_launch_info``: the seed-filter launches of this scanner since it was made or reset -- how
+        many, how many found the scan in front still running, how many published ahead of their survivors -- and of the
+        last one the grid and block of kvq_verify_survivors, the grid cap and which it was, the CUs and the live scan
+        objects.  All zero (``grid_cap_kind`` None) while there was no such launch.  Host-side facts: no device work"""
+        out = (C.c_int64 * 10)()
+        _lib.lib().kvq_scan_launch_info(self.h, out)
+        d = dict(zip(self.LAUNCH_INFO, (int(x) for x in out)))
+        d['grid_cap_kind'] = self.GRID_CAP_KINDS[d['grid_cap_kind']]
+        d['last_beside'] = bool(d['last_beside'])
+        return d
+
     def index_device(self, d_ptr, nbytes, chunk_off, cap=None):
         """(measurement) ``kvq_scan_index_device``: the exact record index of a batch in device memory -> (R, records per chunk,
         nl4 as an (n, 4) array, rec_start), n = min(R, cap); ``cap`` None: a quarter of the batch's bytes, which holds any index"""
