@@ -490,6 +490,57 @@ int32_t        kvq_adapt_host_mm(const uint8_t *text, int64_t nbytes, const int6
 int32_t        kvq_clip_host_mm(uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks,
                                 const uint8_t *const *probes, const int32_t *lens, int32_t n, int32_t per, int64_t *out);
 
+/* ---- the reads the scan saw, as FastQ text: EVERY RECORD CUT TO WHAT THE TRIM LEAVES OF IT ----
+ * EMIT(text, chunk_off, amin, min_length): the record set is the profile's (every complete four-newline record of every chunk,
+ * newlines at n0 < n1 < n2 < n3); r0 is the record's first byte: the byte behind the n3 of the record in front of it, or the
+ * chunk's first byte.  Per record, in stream order:
+ *   name = text[r0, n0) less one trailing '\r';  bases = text[n0 + 1, n1);  scores = text[n2 + 1, n3) -- both raw.
+ *   len(bases) != len(scores): the record is MISMATCHED, dropped and counted.
+ *   else (start, length) is the scan's trim of the score line (workhorse.c:1055-1068: the longest run of bytes >= amin compared as
+ *   signed chars, the line's newline fed too, the first of equal runs), over the whole line, however long.
+ *   length < min_length: the record is SHORT, dropped and counted.
+ *   else it is EMITTED as  name '\n' bases[start, start + length) "\n+\n" scores[start, start + length) '\n'  -- the third line is
+ *   always a bare '+'.  min_length == 0 keeps every well-formed record (with empty lines where nothing survives): the files of
+ *   two mates stay in step record for record.
+ * An emitted record is at most its input record plus one byte: a batch of nbytes bytes and nrec records emits at most
+ * nbytes + nrec bytes, and there is no overflow.
+ * THE RESULT: the emitted text, and one flat int64 array of kvq_emit_len() = 8 words, every word but [0] a sum over the records:
+ *   [0] n = the min_length in effect    [1] records    [2] emitted    [3] short    [4] mismatched
+ *   [5] sum of len(bases) over all records    [6] sum of length over the emitted records    [7] bytes of emitted text
+ *   [1] == [2] + [3] + [4];  [7] == the length of the text;  [1] == the profile's records when a profile is on.
+ * THE CONTRACT WITH THE CLIP: the emit of `text` with the clip on is the emit of MASK(text) without it (the emit runs behind the
+ * clip and behind the scan, on the batch's first pass only); the emitted scores never hold a byte of the mask: they are a run of
+ * bytes >= Amin, and the clip refuses an Amin that is not above '!'.
+ * The emit does not repeat the scan's '@' / '+' checks: a call that ends in KVQ_ERR_FORMAT ends so as before, and what it has
+ * emitted until then is unspecified.
+ * kvq_scan_set_emit: on != 0 turns the emit on with min_length (< 0: the table's minreadlength), on == 0 turns it off; before
+ * the first batch or after kvq_scan_reset, as kvq_scan_set_cycles.  It needs no profile and is allowed beside every other option;
+ * with a communicator it is KVQ_ERR_RUNTIME, as the records are.  amin is the table's Amin.  Off, nothing is enqueued or allocated.
+ * THE SINK: a host buffer that grows -- kvq_scan_emitted hands out its bytes (valid after kvq_scan_finish until the next reset;
+ * KVQ_ERR_RUNTIME before) -- or, after kvq_scan_set_emit_fd(s, fd) with fd >= 0, that file descriptor, which stays the caller's
+ * (fd < 0: the host buffer again; the call needs the emit on).  The sink and the words are cleared wherever the hit arena is --
+ * a regular file is truncated to zero and sought to its start; a pipe cannot take anything back --, so a batch that runs again after an arena overflow (a device batch
+ * replayed inside kvq_scan_finish, host batches fed again, kvq_findseqs reading its files again) is emitted once.  A batch
+ * whose speculation failed is emitted by its first pass alone.  Every batch waits on the host once for its byte count.
+ * kvq_scan_emit: the words (valid after kvq_scan_finish until the next reset), NULL when the option is off.
+ * kvq_scan_emit_guard (measurement): the store of every batch lies between two blocks of 64 guard bytes, the one behind it
+ * right behind the batch's last emitted byte; the number of guard bytes found changed since the last reset (-1: the emit is off). */
+enum { KVQ_EMIT_N = 0, KVQ_EMIT_RECORDS = 1, KVQ_EMIT_EMITTED = 2, KVQ_EMIT_SHORT = 3, KVQ_EMIT_MISMATCHED = 4, KVQ_EMIT_BASES_IN = 5,
+       KVQ_EMIT_BASES_OUT = 6, KVQ_EMIT_BYTES_OUT = 7, KVQ_EMIT_WORDS = 8 };
+int64_t        kvq_emit_len(void);
+int32_t        kvq_scan_set_emit(kvq_scan *s, int32_t on, int32_t min_length);
+int32_t        kvq_scan_set_emit_fd(kvq_scan *s, int32_t fd);
+int32_t        kvq_scan_emitted(const kvq_scan *s, const uint8_t **text, int64_t *nbytes);
+const int64_t *kvq_scan_emit(const kvq_scan *s);
+int64_t        kvq_scan_emit_guard(const kvq_scan *s);
+double         kvq_scan_emit_kernel_ms(const kvq_scan *s);   /* GPU time of kvq_emit_size, the prefix sum and kvq_emit_copy (0 when the emit is off) */
+/* host only, plain C++: the CPU twin of the emit over the same definition -- test infrastructure and the definition in running
+ * code, not a fallback.  Arguments as for kvq_profile_host; amin a byte compared as a signed char, min_length >= 0.  Writes the
+ * emitted text to out_text[0, out_cap) and returns its length, or -1 (bad arguments; out_cap too small for what the text emits:
+ * nbytes + the number of records always holds it).  ADDS into out_words[0, kvq_emit_len()), but for [0], which it sets. */
+int64_t        kvq_emit_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int32_t amin, int32_t min_length,
+                             uint8_t *out_text, int64_t out_cap, int64_t *out_words);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -722,6 +773,17 @@ typedef struct kvq_find_opts_adapters_mm {
     kvq_find_opts_adapters a;            /* a.base.size: sizeof(kvq_find_opts_adapters_mm) */
     int32_t  mismatch_per;
 } kvq_find_opts_adapters_mm;
+/* KVQ_FIND_EMIT: kvq_scan_set_emit(1, min_length) for the call, the sink the file `path`, which the call creates or truncates:
+ * every file of the call goes to the one output, in order (kvq_scan_emit after the call).  min_length and path ride behind the
+ * mismatch rate in a structure that begins with kvq_find_opts_adapters_mm, read only with the flag and only when base.size covers
+ * it -- otherwise "bad size"; the bytes in front stay what they are, and the blocks in front are read only under their own flags
+ * (a caller without probes leaves them zero).  min_length < 0: the configured minreadlength.  It is tied to no other flag. */
+#define KVQ_FIND_EMIT 8192u
+typedef struct kvq_find_opts_emit {
+    kvq_find_opts_adapters_mm m;         /* m.a.base.size: sizeof(kvq_find_opts_emit) */
+    int32_t  min_length;
+    const char *path;
+} kvq_find_opts_emit;
 kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
                             const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts);
 

@@ -21,7 +21,8 @@ FIND_OVERREPRESENTED = 512                                       # ... the overr
 FIND_ADAPTERS = 1024                                             # ... the adapter content (with FIND_PROFILE; the probes in FindOptsAdapters)
 FIND_CLIP = 2048                                                 # ... the adapter clip ahead of the trim (no profile needed; the same probe block)
 FIND_ADAPTER_MISMATCHES = 4096                                   # ... the probes of both tolerate mismatches (the rate in FindOptsAdaptersMm)
-READ_STATS, READ_DUPLICATION = 1, 2                            # kvq_scan_set_read_stats
+FIND_EMIT = 8192                                                 # ... the trimmed reads as FastQ text (min_length and the output's path in FindOptsEmit)
+READ_STATS, READ_DUPLICATION = 1, 2                           # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
 # kvq_scan_path: a batch took the seed-filter kernel / the exhaustive kernels; a whole batch / the records of skipped tiles were redone;
@@ -60,6 +61,11 @@ class FindOptsAdapters(C.Structure):
 class FindOptsAdaptersMm(C.Structure):
     """kvq_find_opts_adapters_mm: kvq_find_opts_adapters, then the mismatch rate of FIND_ADAPTER_MISMATCHES"""
     _fields_ = [('a', FindOptsAdapters), ('mismatch_per', C.c_int32)]
+
+
+class FindOptsEmit(C.Structure):
+    """kvq_find_opts_emit: kvq_find_opts_adapters_mm, then min_length and the output's path of FIND_EMIT"""
+    _fields_ = [('m', FindOptsAdaptersMm), ('min_length', C.c_int32), ('path', C.c_char_p)]
 
 
 class GzipReport(C.Structure):
@@ -165,6 +171,14 @@ PROTOTYPES = {
     'kvq_scan_adapter_mismatches': (i32, [vp]),
     'kvq_adapt_host_mm': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, i32, P(i64)]),
     'kvq_clip_host_mm': (i32, [vp, i64, P(i64), i64, P(cp), P(i32), i32, i32, P(i64)]),
+    'kvq_emit_len': (i64, []),
+    'kvq_scan_set_emit': (i32, [vp, i32, i32]),
+    'kvq_scan_set_emit_fd': (i32, [vp, i32]),
+    'kvq_scan_emitted': (i32, [vp, P(vp), P(i64)]),
+    'kvq_scan_emit': (P(i64), [vp]),
+    'kvq_scan_emit_guard': (i64, [vp]),
+    'kvq_scan_emit_kernel_ms': (C.c_double, [vp]),
+    'kvq_emit_host': (i64, [vp, i64, P(i64), i64, i32, i32, vp, i64, P(i64)]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

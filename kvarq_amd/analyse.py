@@ -47,6 +47,7 @@ class Analyser(object):
         self.records = None                     # the FastQ record of every hit, when ``scan`` kept them (records=True)
         self.profile = None                     # the profile of the input, when ``scan`` took one (profile=<cutoffs>)
         self.clip = None                        # what the adapter clip did, when ``scan`` clipped (clip=<probes>): a ``profile.Clip``
+        self.emit = None                        # what the emit wrote, when ``scan`` emitted the trimmed reads (emit=<path>): a ``profile.Emit``
         self.results = {}                       # testsuite interpretation is out of scope: stays empty
         self.scantime = -1
 
@@ -74,7 +75,8 @@ class Analyser(object):
         (``info['profile']['cycles']``), ``per_read=True`` / ``duplication=True`` the per-read distributions / the
         duplication (``info['profile']['per_read']`` / ``['duplication']``), ``overrepresented=True`` the overrepresented
         sequences (``info['profile']['overrepresented']``), ``adapters=`` the adapter content (``info['profile']['adapters']``); ``clip=`` masks the
-        scores of adapters ahead of the trim and keeps what it did in ``self.clip``; ``adapter_mismatches=`` lets the probes of both tolerate mismatches; ``long_reads``: as for ``engine.findseqs``,
+        scores of adapters ahead of the trim and keeps what it did in ``self.clip``; ``adapter_mismatches=`` lets the probes of both tolerate mismatches; ``emit=<path>`` (with ``emit_min=``) writes
+        the trimmed reads there as FastQ and keeps what it wrote in ``self.emit``; ``long_reads``: as for ``engine.findseqs``,
         which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
@@ -93,6 +95,7 @@ class Analyser(object):
         self.records = ret.get('records')
         self.profile = ret.get('profile')
         self.clip = ret.get('clip')
+        self.emit = ret.get('emit')
         self.scantime = time.time() - t0
         self.update_coverages()
 

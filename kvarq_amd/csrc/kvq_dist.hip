@@ -242,6 +242,10 @@ extern "C" int32_t kvq_scan_set_comm(kvq_scan *s, kvq_comm *c)
         kvq_set_error(KVQ_ERR_RUNTIME, "the profile is not reduced across ranks: a scan that keeps one cannot take a communicator");
         return KVQ_ERR_RUNTIME;
     }
+    if (c && s->passes[KVQ_PASS_EMIT].on) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "the emitted reads are not gathered across ranks: a scan that emits them cannot take a communicator");
+        return KVQ_ERR_RUNTIME;
+    }
     if (c) {
         int rc;
         if ((rc = s->d_finish.ensure(sizeof(KvqFinishState) + 256))) return rc;

@@ -5,6 +5,7 @@
 #include "kvq_host.h"
 
 #include <atomic>
+#include <fcntl.h>
 #include <mutex>
 #include <signal.h>
 #include <string.h>
@@ -217,6 +218,13 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         mismatch_per = ((const kvq_find_opts_adapters_mm *)opts)->mismatch_per;
         if (!adapt_per_ok("kvq_findseqs_opts", mismatch_per)) return nullptr;
     }
+    // min_length and the path of KVQ_FIND_EMIT ride behind the mismatch rate: read only with the flag, and only when the size covers them
+    int32_t emit_min = -1; const char *emit_path = nullptr;
+    if (flags & KVQ_FIND_EMIT) {
+        if (!opts || opts->size < sizeof(kvq_find_opts_emit)) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: bad size"); return nullptr; }
+        emit_min = ((const kvq_find_opts_emit *)opts)->min_length; emit_path = ((const kvq_find_opts_emit *)opts)->path;
+        if (!emit_path || !emit_path[0]) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_EMIT needs the path of the output"); return nullptr; }
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -257,8 +265,20 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
               kvq_scan_set_overrepresented(s, (flags & KVQ_FIND_OVERREPRESENTED) ? 1 : 0) ||
               kvq_scan_set_adapters(s, probes, probe_lens, (flags & KVQ_FIND_ADAPTERS) ? nprobes : 0) ||
               kvq_scan_set_clip(s, probes, probe_lens, (flags & KVQ_FIND_CLIP) ? nprobes : 0) ||
-              kvq_scan_set_adapter_mismatches(s, mismatch_per))) {
+              kvq_scan_set_adapter_mismatches(s, mismatch_per) ||
+              kvq_scan_set_emit(s, (flags & KVQ_FIND_EMIT) ? 1 : 0, emit_min))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
+    }
+    // the one output of KVQ_FIND_EMIT: every file of the call goes to it, in order (a rescan after an arena overflow empties it: pass_clear)
+    int emit_fd = -1;
+    if (s && emit_path) {
+        emit_fd = open(emit_path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+        if (emit_fd < 0 || kvq_scan_set_emit_fd(s, emit_fd)) {
+            if (emit_fd < 0) kvq_set_error(KVQ_ERR_IO, "cannot open '%s' for the emitted reads", emit_path);
+            else close(emit_fd);
+            emit_fd = -1;
+            kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
+        }
     }
     const double tf1 = now_ms();
     // the two pinned host buffers outlive the call: pinning and unpinning 130 MB costs more than
@@ -315,6 +335,11 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
     }
     const double tf3 = now_ms();
     if (s && s->stream) (void)hipStreamSynchronize(s->stream);        // nothing may still be reading the host buffers
+    if (emit_fd >= 0) {
+        // (the scan object may be kept for the next call: it must not hold the descriptor of a file this call closes)
+        emit_detach_fd(s);
+        if (close(emit_fd) != 0 && !kvq_error_code()) kvq_set_error(KVQ_ERR_IO, "cannot write the emitted reads to '%s'", emit_path);
+    }
     if (g_timing) fprintf(stderr, "findseqs: table+scan %.1f  pinned alloc %.1f  passes %.1f  free %.1f ms\n", tf1 - tf0, tf2 - tf1, tf3 - tf2, now_ms() - tf3);
     if (s && (route == ROUTE_BGZF || route == ROUTE_GZIP)) s->path_bits |= 16;      // (kvq_scan_path bit 4: the text was inflated on the device;
                                                                                     // bit 5, set by GzipProducer: a file took the speculative route)

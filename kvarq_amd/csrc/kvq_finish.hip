@@ -407,6 +407,7 @@ extern "C" double kvq_scan_reads_kernel_ms(const kvq_scan *s) { return s->passes
 extern "C" double kvq_scan_over_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_OVER].ms; }
 extern "C" double kvq_scan_adapt_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_ADAPT].ms; }
 extern "C" double kvq_scan_clip_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_CLIP].ms; }
+extern "C" double kvq_scan_emit_kernel_ms(const kvq_scan *s) { return s->passes[KVQ_PASS_EMIT].ms; }
 // (measurement) ms from the end of a's last main kernel to the start of b's first one (both finished, neither reset since); < 0: unknown
 extern "C" double kvq_scan_gap_ms(const kvq_scan *a, const kvq_scan *b)
 {

@@ -143,7 +143,8 @@ int kvq_comm_max_status(kvq_comm *c, unsigned long long mine, unsigned long long
 // An input pass: a kernel that every batch runs once over its exact record index and that adds to one device array, which the
 // tail of the scan brings to the host.  The cycles' array has the kernel's own scratch word behind the words that land.
 // (the clip is no pass behind the scan: its kernel runs in front of it and needs no profile -- clip_text in kvq_scan.hip; its array shares the lifecycle)
-enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASS_ADAPT, KVQ_PASS_CLIP, KVQ_PASSES };
+// (the emit is the last pass behind the scan and needs no profile either -- emit_enqueue in kvq_profile.hip; its eight words share the lifecycle)
+enum { KVQ_PASS_PROFILE, KVQ_PASS_CYCLES, KVQ_PASS_READS, KVQ_PASS_OVER, KVQ_PASS_ADAPT, KVQ_PASS_CLIP, KVQ_PASS_EMIT, KVQ_PASSES };
 typedef std::pair<hipEvent_t, hipEvent_t> KvqEventPair;
 struct KvqPass {
     bool on = false;
@@ -256,6 +257,16 @@ struct kvq_scan {
     int32_t clip_n = 0; uint8_t clip_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t clip_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
     // one mismatch per this many bases in the probes of both (kvq_scan_set_adapter_mismatches): 0, the exact rule, or 10 .. 32
     int32_t adapt_per = 0;
+    // the emit (kvq_scan_set_emit): its words are passes[KVQ_PASS_EMIT] (the array has the batch's total and the copies of
+    // the guards behind the words that land).  Per record what kvq_emit_size says of it and where its output begins, the block sums of
+    // the prefix sum, the store of a batch (nbytes + nrec bytes between two guards: KvqEmitLayout), reused batch after batch; a pinned
+    // buffer of two halves through which the emitted bytes reach the sink: the host buffer, or the caller's file descriptor
+    int32_t emit_min = 0;
+    DevBuf d_emit_rec, d_emit_off, d_emit_bsum, d_emit_store;
+    uint8_t *emit_pin = nullptr; size_t emit_pin_cap = 0;
+    hipEvent_t emit_ev[2] = { nullptr, nullptr };
+    std::vector<uint8_t> emit_sink; int emit_fd = -1;
+    int64_t emit_guard_bad = 0;
 };
 
 // kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal

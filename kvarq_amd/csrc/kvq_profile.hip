@@ -1,9 +1,10 @@
 // kvarq_amd/csrc/kvq_profile.hip -- the input passes (include/kvarq_hip.h, DESIGN sections 13, 14, 16, 17 and 18), host side: the profile, the
-// per-cycle counts, the per-read statistics, the overrepresented sequences, the adapter content and the adapter clip (section 19), with the mismatch rate of their probes (section 20), as options of a scan object, the steps of their common lifecycle, the launch of
+// per-cycle counts, the per-read statistics, the overrepresented sequences, the adapter content and the adapter clip (section 19), with the mismatch rate of their probes (section 20), and the emit of the trimmed reads (section 21), as options of a scan object, the steps of their common lifecycle, the launch of
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
 #include <array>
 #include <string.h>
+#include <sys/stat.h>
 
 // ---- the lifecycle of an input pass: what the three share, written once ----
 // make or grow the device array (d_bytes, none: 0) and the landing buffer; `words` of the array land
@@ -90,6 +91,16 @@ static int pass_clear(kvq_scan *s, int which)
     if (p.d_bytes) KVQ_HIP(hipMemsetAsync(p.d.p, 0, p.d_bytes, s->stream));
     if (which == KVQ_PASS_READS && (s->reads_mode & KVQ_READ_DUPLICATION)) KVQ_HIP(hipMemsetAsync(s->d_dup.p, 0, KvqDupLayout::bytes(s->dup_slots), s->stream));
     if (which == KVQ_PASS_OVER) s->over_seen = 0;            // (the table is the pass's array: empty again, and the next record is number 0)
+    if (which == KVQ_PASS_EMIT) {
+        // the sink is empty again: a batch that runs again is emitted once (no batch is in flight here: every batch's emit ends with a host wait)
+        s->emit_sink.clear(); s->emit_guard_bad = 0;
+        // (a regular file is truncated and sought to its start; what is no such file -- a pipe, a terminal -- cannot take anything back)
+        struct stat st;
+        if (s->emit_fd >= 0 && fstat(s->emit_fd, &st) == 0 && S_ISREG(st.st_mode) && (ftruncate(s->emit_fd, 0) != 0 || lseek(s->emit_fd, 0, SEEK_SET) != 0)) {
+            kvq_set_error(KVQ_ERR_IO, "cannot empty the file of the emitted reads");
+            return KVQ_ERR_IO;
+        }
+    }
     return KVQ_OK;
 }
 static int passes_clear(kvq_scan *s)
@@ -152,6 +163,7 @@ static void passes_landed(kvq_scan *s)
         s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_N] = s->clip_n;
         if (s->adapt_per) s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_PER] = s->adapt_per;
     }
+    if (s->passes[KVQ_PASS_EMIT].on) s->passes[KVQ_PASS_EMIT].h[KVQ_EMIT_N] = s->emit_min;      // (the word that is no sum)
 }
 // what an accessor hands out: the copy of a pass that is on, of a finished scan
 static const int64_t *pass_result(const kvq_scan *s, int which)
@@ -499,3 +511,153 @@ static int clip_enqueue(kvq_scan *s, uint8_t *d_data, uint64_t R)
 }
 
 extern "C" const int64_t *kvq_scan_clip(const kvq_scan *s) { return pass_result(s, KVQ_PASS_CLIP); }
+
+// ---- the reads the scan saw, as FastQ text ----
+// Its eight words go through the lifecycle above; behind them in the pass's array lies the byte count of the batch in flight.
+// Everything else is the emit's own: what kvq_emit_size says per record, the prefix sum's block sums, the offsets, the store.
+extern "C" int64_t kvq_emit_len(void) { return KVQ_EMIT_WORDS; }
+
+// where the pieces lie: the pass's device array (the words that land, the batch's total), its pinned buffer (the landing words,
+// the total, the copies of the two guards), the store (a guard, the batch's bytes, a guard right behind the last of them)
+struct KvqEmitLayout {
+    static constexpr size_t D_TOTAL = KVQ_EMIT_WORDS, D_WORDS = 16, PIN_TOTAL = KVQ_EMIT_WORDS, PIN_GUARDS = 16, PIN_WORDS = 32;
+    static constexpr size_t GUARD = 64, HALF = 8u << 20;
+    static constexpr int GUARD_BYTE = 0xA5;
+    static size_t store_bytes(size_t cap) { return GUARD + cap + GUARD + 16; }
+};
+static_assert(KvqEmitLayout::PIN_GUARDS * 8 + 2 * KvqEmitLayout::GUARD <= KvqEmitLayout::PIN_WORDS * 8, "the pieces of the emit's pinned buffer overlap");
+
+static void emit_off(kvq_scan *s)
+{
+    pass_off(s, s->passes[KVQ_PASS_EMIT]);               // (waits for the stream where there is anything to wait for)
+    for (DevBuf *b : { &s->d_emit_rec, &s->d_emit_off, &s->d_emit_bsum, &s->d_emit_store }) b->release();
+    if (s->emit_pin) pinned_give(s->emit_pin, s->emit_pin_cap);
+    s->emit_pin = nullptr; s->emit_pin_cap = 0;
+    for (hipEvent_t &e : s->emit_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    s->emit_sink.clear(); s->emit_sink.shrink_to_fit();
+    s->emit_fd = -1; s->emit_min = 0; s->emit_guard_bad = 0;
+}
+
+extern "C" int32_t kvq_scan_set_emit(kvq_scan *s, int32_t on, int32_t min_length)
+{
+    int rc;
+    kvq_clear_error();
+    if ((rc = scan_idle(s, "kvq_scan_set_emit"))) return rc;
+    if (!on) { emit_off(s); return KVQ_OK; }
+    if (s->comm) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "the emitted reads are not gathered across ranks: a scan with a communicator cannot emit them");
+        return KVQ_ERR_RUNTIME;
+    }
+    if ((rc = pass_make(s->passes[KVQ_PASS_EMIT], KvqEmitLayout::D_WORDS * 8, KVQ_EMIT_WORDS, KvqEmitLayout::PIN_WORDS * 8))) { emit_off(s); return rc; }
+    if (!s->emit_pin) {
+        s->emit_pin = (uint8_t *)pinned_take(2 * KvqEmitLayout::HALF, &s->emit_pin_cap);
+        if (!s->emit_pin) { emit_off(s); kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
+    }
+    for (hipEvent_t &e : s->emit_ev)
+        if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { e = nullptr; emit_off(s); kvq_set_error(KVQ_ERR_DEVICE, "hipEventCreate failed"); return KVQ_ERR_DEVICE; }
+    s->emit_min = min_length < 0 ? std::max<int32_t>(s->t->cfg.minreadlength, 0) : min_length;
+    return pass_clear(s, KVQ_PASS_EMIT);
+}
+
+extern "C" int32_t kvq_scan_set_emit_fd(kvq_scan *s, int32_t fd)
+{
+    kvq_clear_error();
+    if (const int rc = scan_idle(s, "kvq_scan_set_emit_fd")) return rc;
+    if (!s->passes[KVQ_PASS_EMIT].on) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_emit_fd: the scan emits nothing (kvq_scan_set_emit first)"); return KVQ_ERR_RUNTIME; }
+    s->emit_fd = fd < 0 ? -1 : fd;
+    return KVQ_OK;
+}
+// the file descriptor is about to be closed by its owner (kvq_findseqs): the sink is the host buffer again, whatever the scan holds
+static void emit_detach_fd(kvq_scan *s) { s->emit_fd = -1; }
+
+// n bytes of emitted text to the sink
+static int emit_append(kvq_scan *s, const uint8_t *p, size_t n)
+{
+    if (s->emit_fd < 0) { s->emit_sink.insert(s->emit_sink.end(), p, p + n); return KVQ_OK; }
+    while (n) {
+        const ssize_t w = write(s->emit_fd, p, n);
+        if (w <= 0) { kvq_set_error(KVQ_ERR_IO, "cannot write the emitted reads"); return KVQ_ERR_IO; }
+        p += w; n -= (size_t)w;
+    }
+    return KVQ_OK;
+}
+
+static int new_event_pair(kvq_scan *s, std::vector<KvqEventPair> &v);     // (kvq_scan.hip)
+
+// The emit of the R records of a batch of nbytes bytes whose index (nl4, rec_start) is on the scan's stream, behind its scan: the
+// sizes, their prefix sum, ONE HOST WAIT for the batch's byte count, the copy into the store, and the store's bytes through the two
+// halves of the pinned buffer to the sink -- the copy of a half runs while the half before it is appended.  The batch's emit is
+// over when this returns: the store and the index are free for the next batch.
+static int emit_enqueue(kvq_scan *s, const uint8_t *d_data, int64_t nbytes, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    int rc;
+    KvqPass &p = s->passes[KVQ_PASS_EMIT];
+    const uint32_t nblocks = (uint32_t)((R + KVQ_EMIT_SCAN_BLOCK - 1) / KVQ_EMIT_SCAN_BLOCK);
+    const size_t cap = (size_t)nbytes + (size_t)R;           // an emitted record is at most its input record plus one byte
+    if ((rc = s->d_emit_rec.ensure((size_t)R * sizeof(KvqEmitRec))) || (rc = s->d_emit_off.ensure((size_t)R * 8)) ||
+        (rc = s->d_emit_bsum.ensure((size_t)nblocks * 8)) || (rc = s->d_emit_store.ensure(KvqEmitLayout::store_bytes(cap)))) return rc;
+    unsigned long long *const d_words = p.d.as<unsigned long long>(), *const d_total = d_words + KvqEmitLayout::D_TOTAL;
+    KvqEmitRec *const d_rec = s->d_emit_rec.as<KvqEmitRec>();
+    uint8_t *const store = s->d_emit_store.as<uint8_t>() + KvqEmitLayout::GUARD;
+    const uint32_t sgrid = (uint32_t)std::min<uint64_t>(nblocks, 2048);                    // (the kernels stride over what there is)
+    if ((rc = new_event_pair(s, p.ev))) return rc;
+    KVQ_HIP(hipEventRecord(p.ev.back().first, s->stream));
+    hipLaunchKernelGGL(kvq_emit_size, dim3((uint32_t)std::min<uint64_t>((R + 4 * KVQ_TRIM_RPW - 1) / (4 * KVQ_TRIM_RPW), 2048)), dim3(256), 0, s->stream, d_data,
+                       s->d_nl4.as<uint32_t>(), s->d_rec_start.as<uint32_t>(), (uint32_t)R, (int32_t)s->t->cfg.Amin, (uint32_t)s->emit_min, d_rec, d_words);
+    hipLaunchKernelGGL(kvq_emit_block_sums, dim3(sgrid), dim3(256), 0, s->stream, (const KvqEmitRec *)d_rec, (uint32_t)R, s->d_emit_bsum.as<unsigned long long>());
+    hipLaunchKernelGGL(kvq_emit_scan_blocks, dim3(1), dim3(256), 0, s->stream, s->d_emit_bsum.as<unsigned long long>(), nblocks, d_total);
+    hipLaunchKernelGGL(kvq_emit_offsets, dim3(sgrid), dim3(256), 0, s->stream, (const KvqEmitRec *)d_rec, (uint32_t)R,
+                       (const unsigned long long *)s->d_emit_bsum.as<unsigned long long>(), s->d_emit_off.as<unsigned long long>());
+    KVQ_HIP(hipGetLastError());
+    KVQ_HIP(hipEventRecord(p.ev.back().second, s->stream));
+    KVQ_HIP(hipMemcpyAsync(p.pin + KvqEmitLayout::PIN_TOTAL, d_total, 8, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipStreamSynchronize(s->stream));
+    const uint64_t total = (uint64_t)p.pin[KvqEmitLayout::PIN_TOTAL];
+    if (total > cap) { kvq_set_error(KVQ_ERR_RUNTIME, "the emit of a batch of %lld bytes and %llu records sized itself at %llu bytes", (long long)nbytes, (unsigned long long)R, (unsigned long long)total); return KVQ_ERR_RUNTIME; }
+    KVQ_HIP(hipMemsetAsync(store - KvqEmitLayout::GUARD, KvqEmitLayout::GUARD_BYTE, KvqEmitLayout::GUARD, s->stream));
+    KVQ_HIP(hipMemsetAsync(store + total, KvqEmitLayout::GUARD_BYTE, KvqEmitLayout::GUARD, s->stream));
+    if (total) {
+        if ((rc = new_event_pair(s, p.ev))) return rc;
+        KVQ_HIP(hipEventRecord(p.ev.back().first, s->stream));
+        hipLaunchKernelGGL(kvq_emit_copy, dim3((uint32_t)std::min<uint64_t>((R + 15) / 16, 2048)), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(),
+                           s->d_rec_start.as<uint32_t>(), (uint32_t)R, (const KvqEmitRec *)d_rec, (const unsigned long long *)s->d_emit_off.as<unsigned long long>(), store);
+        KVQ_HIP(hipGetLastError());
+        KVQ_HIP(hipEventRecord(p.ev.back().second, s->stream));
+    }
+    uint8_t *const guards = (uint8_t *)(p.pin + KvqEmitLayout::PIN_GUARDS);
+    KVQ_HIP(hipMemcpyAsync(guards, store - KvqEmitLayout::GUARD, KvqEmitLayout::GUARD, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipMemcpyAsync(guards + KvqEmitLayout::GUARD, store + total, KvqEmitLayout::GUARD, hipMemcpyDeviceToHost, s->stream));
+    const size_t H = KvqEmitLayout::HALF;
+    size_t prev_n = 0;
+    for (uint64_t at = 0, i = 0; at < total; at += H, i++) {
+        const size_t n = (size_t)std::min<uint64_t>(H, total - at);
+        KVQ_HIP(hipMemcpyAsync(s->emit_pin + (i & 1) * H, store + at, n, hipMemcpyDeviceToHost, s->stream));
+        KVQ_HIP(hipEventRecord(s->emit_ev[i & 1], s->stream));
+        if (i) {
+            KVQ_HIP(hipEventSynchronize(s->emit_ev[(i - 1) & 1]));
+            if ((rc = emit_append(s, s->emit_pin + ((i - 1) & 1) * H, prev_n))) { (void)hipStreamSynchronize(s->stream); return rc; }
+        }
+        prev_n = n;
+    }
+    KVQ_HIP(hipStreamSynchronize(s->stream));
+    if (total && (rc = emit_append(s, s->emit_pin + (((total - 1) / H) & 1) * H, prev_n))) return rc;
+    for (size_t i = 0; i < 2 * KvqEmitLayout::GUARD; i++) s->emit_guard_bad += guards[i] != (uint8_t)KvqEmitLayout::GUARD_BYTE;
+    return KVQ_OK;
+}
+
+extern "C" const int64_t *kvq_scan_emit(const kvq_scan *s) { return pass_result(s, KVQ_PASS_EMIT); }
+extern "C" int64_t kvq_scan_emit_guard(const kvq_scan *s) { return s->passes[KVQ_PASS_EMIT].on ? s->emit_guard_bad : -1; }
+extern "C" int32_t kvq_scan_emitted(const kvq_scan *s, const uint8_t **text, int64_t *nbytes)
+{
+    kvq_clear_error();
+    if (text) *text = nullptr;
+    if (nbytes) *nbytes = 0;
+    if (!s->passes[KVQ_PASS_EMIT].on || !s->finished) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_emitted: only on a finished scan that kvq_scan_set_emit was turned on for");
+        return KVQ_ERR_RUNTIME;
+    }
+    if (text && !s->emit_sink.empty()) *text = s->emit_sink.data();
+    if (nbytes) *nbytes = (int64_t)s->emit_sink.size();
+    return KVQ_OK;
+}

@@ -246,7 +246,9 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
     if (s->ev_chain) (void)hipEventDestroy(s->ev_chain);
     if (s->pin_rec) pinned_give(s->pin_rec, s->pin_rec_cap);
     for (KvqPass &p : s->passes) { if (p.pin) pinned_give(p.pin, p.pin_cap); p.d.release(); }
-    DevBuf *bufs[] = { &s->d_dup, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
+    if (s->emit_pin) pinned_give(s->emit_pin, s->emit_pin_cap);
+    for (hipEvent_t e : s->emit_ev) if (e) (void)hipEventDestroy(e);
+    DevBuf *bufs[] = { &s->d_emit_rec, &s->d_emit_off, &s->d_emit_bsum, &s->d_emit_store, &s->d_dup, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
                        &s->d_rec_start, &s->d_read_off, &s->d_read_len, &s->d_arena, &s->d_blob, &s->d_small, &s->d_stage, &s->d_stage_b };
     for (DevBuf *b : bufs) b->release();
     s->pool.release();
@@ -589,7 +591,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
         if (B.nrec < 0 && (rc = index_records(s, B))) return rc;
         for (int i = 0; i < KVQ_PASSES && B.nrec > 0; i++) {
             KvqPass &p = s->passes[i];
-            if (!p.on || i == KVQ_PASS_CLIP) continue;     // (the clip has run in front of the scan: clip_text)
+            if (!p.on || i == KVQ_PASS_CLIP || i == KVQ_PASS_EMIT) continue;     // (the clip has run in front of the scan: clip_text; the emit follows below, profile or not)
             if ((rc = new_event_pair(s, p.ev))) return rc;
             KVQ_HIP(hipEventRecord(p.ev.back().first, s->stream));
             switch (i) {
@@ -602,6 +604,12 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
             if (rc) return rc;
             KVQ_HIP(hipEventRecord(p.ev.back().second, s->stream));
         }
+    }
+    // the emit (kvq_scan_set_emit): every batch once, by its first pass, like the profile -- behind the scan and
+    // behind clip_text, whose mask it reads, from the index the batch has (its own where nobody has made one); it needs no profile
+    if (s->passes[KVQ_PASS_EMIT].on && !exhaustive_only) {
+        if (B.nrec < 0 && (rc = index_records(s, B))) return rc;
+        if (B.nrec > 0 && (rc = emit_enqueue(s, d_data, B.nbytes, (uint64_t)B.nrec))) return rc;
     }
     KVQ_HIP(hipEventRecord(s->ev_all.back().second, s->stream));
     KVQ_HIP(hipGetLastError());

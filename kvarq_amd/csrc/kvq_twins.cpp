@@ -1,7 +1,8 @@
-// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes and of the adapter clip (include/kvarq_hip.h, DESIGN sections 13,
-// 14, 16, 17, 18, 19 and 20): the definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records, kvq_over_records,
-// kvq_adapt_records, kvq_clip_records, kvq_adapt_records_mm and kvq_clip_records_mm in plain C++ (test infrastructure, never a
-// fallback).  Nothing of HIP: the file also compiles on its own.  One argument check and one record walk serve all eight.
+// kvarq_amd/csrc/kvq_twins.cpp -- the CPU twins of the input passes, of the adapter clip and of the emit (include/kvarq_hip.h, DESIGN
+// sections 13, 14, 16, 17, 18, 19, 20 and 21): the definitions of kvq_profile_records, kvq_profile_cycles, kvq_reads_records,
+// kvq_over_records, kvq_adapt_records, kvq_clip_records, kvq_adapt_records_mm, kvq_clip_records_mm and of the kernels of
+// kernels_emit.hip in plain C++ (test infrastructure, never a fallback).  Nothing of HIP: the file also compiles on its own.  One
+// argument check serves all nine and one record walk the first eight (the emit walks with the record's first byte beside its newlines).
 #include "../../include/kvarq_hip.h"
 #include "kvq_dup_hash.h"
 #include <algorithm>
@@ -362,4 +363,51 @@ extern "C" int32_t kvq_profile_host(const uint8_t *text, int64_t nbytes, const i
         }
     });
     return KVQ_OK;
+}
+
+// ---- the emitted reads ----
+extern "C" int64_t kvq_emit_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int32_t amin_, int32_t min_length,
+                                 uint8_t *out_text, int64_t out_cap, int64_t *out_words)
+{
+    if (!twin_args("kvq_emit_host", out_words && min_length >= 0 && out_cap >= 0 && (out_cap == 0 || out_text), nbytes, chunk_off, nchunks)) return -1;
+    const int amin = (int8_t)amin_;
+    int64_t at = 0; bool full = false;
+    out_words[KVQ_EMIT_N] = min_length;
+    for (int64_t c = 0; c < nchunks; c++) {
+        // for_each_record's walk, with the record's first byte beside its newlines
+        int64_t nl[4], r0 = chunk_off[c]; int have = 0;
+        for (int64_t i = chunk_off[c]; i < chunk_off[c + 1]; i++) {
+            if (text[i] != '\n') continue;
+            nl[have++] = i;
+            if (have < 4) continue;
+            have = 0;
+            const int64_t n0 = nl[0], n1 = nl[1], n2 = nl[2], n3 = nl[3], start0 = r0;
+            r0 = n3 + 1;
+            const int64_t L = n1 - n0 - 1, Q = n3 - n2 - 1;
+            out_words[KVQ_EMIT_RECORDS]++; out_words[KVQ_EMIT_BASES_IN] += L;
+            if (L != Q) { out_words[KVQ_EMIT_MISMATCHED]++; continue; }
+            // workhorse.c:1055-1068 over the score line and its newline: the first of the longest runs that a low byte closes
+            int64_t run = n2 + 1, best = 0, bstart = n2 + 1;
+            for (int64_t j = n2 + 1; j <= n3; j++) {
+                if ((int)(int8_t)text[j] >= amin) { if (run < 0) run = j; }
+                else { if (run >= 0 && j - run > best) { best = j - run; bstart = run; } run = -1; }
+            }
+            if (best < min_length) { out_words[KVQ_EMIT_SHORT]++; continue; }
+            const int64_t start = bstart - (n2 + 1);
+            const int64_t name = n0 - start0 - (n0 > start0 && text[n0 - 1] == '\r' ? 1 : 0);
+            const int64_t bytes = name + 2 * best + 5;
+            out_words[KVQ_EMIT_EMITTED]++; out_words[KVQ_EMIT_BASES_OUT] += best; out_words[KVQ_EMIT_BYTES_OUT] += bytes;
+            if (at + bytes > out_cap) { full = true; at += bytes; continue; }
+            uint8_t *o = out_text + at;
+            if (name) memcpy(o, text + start0, (size_t)name);
+            o += name; *o++ = '\n';
+            if (best) memcpy(o, text + n0 + 1 + start, (size_t)best);
+            o += best; *o++ = '\n'; *o++ = '+'; *o++ = '\n';
+            if (best) memcpy(o, text + n2 + 1 + start, (size_t)best);
+            o += best; *o++ = '\n';
+            at += bytes;
+        }
+    }
+    if (full) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_emit_host: the text emits %lld bytes, out_cap is %lld", (long long)at, (long long)out_cap); return -1; }
+    return at;
 }

@@ -229,6 +229,16 @@ def findseqs(fname, sequences, *, inflate='host', **options):
     the adapter's first base; ``Adapters.first_mismatches`` tells how many of them differed in 0 .. 3 places.
     None, False or 0: the probes match byte for byte, as without the option.
 
+    emit='out.fastq' (not in the reference): the reads as the scan saw them are written to that file as
+    FastQ, every file of the call to the one output, in order: every record cut to the part the quality trim leaves of it -- the
+    longest run of scores at or above the configured Amin, behind ``clip`` ending in front of the adapter too -- as name, bases,
+    a bare '+', scores.  emit_min=N keeps the reads of N bases and more (None: the configured minreadlength; 0 keeps every
+    record with matching lines, empty where nothing survives, so that the files of two mates stay in step); records whose bases
+    and scores differ in length are dropped.  The compaction runs on the GPU behind the scan.  The dict gains 'emit'
+    (``profile.Emit``: ``records``, ``emitted``, ``short``, ``mismatched``, ``bases_in``, ``bases_out``, ``bytes_out``,
+    ``words``) and 'emit_kernel_ms'.  It needs no profile.  A call that raises FastqFileFormatException
+    raises it as before; what the file holds then is unspecified.
+
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
     no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are
@@ -308,6 +318,10 @@ def findseqs(fname, sequences, *, inflate='host', **options):
             from . import profile as profile_
             out['clip'] = profile_.clip_from_scan(L, h, (opt.clip_names, opt.clip))
             out['clip_kernel_ms'] = L.kvq_scan_clip_kernel_ms(h)
+        if opt.emit is not None:
+            from . import profile as profile_
+            out['emit'] = profile_.emit_from_scan(L, h)
+            out['emit_kernel_ms'] = L.kvq_scan_emit_kernel_ms(h)
         return out
     finally:
         if h:

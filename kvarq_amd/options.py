@@ -1,6 +1,6 @@
 """
 The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
-``duplication``, ``overrepresented``, ``adapters``, ``clip``, ``adapter_mismatches`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+``duplication``, ``overrepresented``, ``adapters``, ``clip``, ``adapter_mismatches``, ``emit``, ``emit_min`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
 everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
 """
 import ctypes as C
@@ -25,6 +25,33 @@ def as_mismatch_per(adapter_mismatches):
     return per
 
 
+def as_emit(emit, emit_min=None):
+    """``(emit, min_length)`` for an ``emit`` and an ``emit_min`` option.  ``emit``: None or False -> None (off); True -> True (the
+    emitted text is handed back); a path (str, bytes, os.PathLike) -> its bytes (the text is streamed there).  ``emit_min``: None ->
+    -1 (the configured minreadlength); an int >= 0 -> itself; anything else, or an ``emit_min`` without ``emit``: ValueError"""
+    import os
+    if emit is None or emit is False:
+        emit = None
+    elif emit is not True:
+        try:
+            emit = os.fsencode(emit)
+        except TypeError:
+            raise ValueError('emit is None or False (off), True, or the path of the output')
+        if not emit:
+            raise ValueError('emit is None or False (off), True, or the path of the output')
+    if emit_min is None:
+        return emit, -1
+    try:
+        m = -1 if isinstance(emit_min, bool) else operator.index(emit_min)
+    except TypeError:
+        m = -1
+    if m < 0 or m > 0x7FFFFFFF:
+        raise ValueError('emit_min is None (the configured minreadlength) or an int >= 0')
+    if emit is None:
+        raise ValueError('emit_min= is the shortest read emit= keeps: give emit= too')
+    return emit, m
+
+
 class ScanOptions(object):
     """``records``: keep the FastQ record of every hit; ``profile``: the cutoffs of the input's profile
     (``profile.as_cutoffs``; True: ``amin``, or the configured Amin; None: no profile) -- a list of byte values here;
@@ -37,10 +64,15 @@ class ScanOptions(object):
     ``clip``, a list of bytes, here; it needs no profile.  ``adapters`` and ``clip`` together must name the same probes (``findseqs``
     has one probe block): otherwise ValueError.  ``adapter_mismatches``: the probes of both tolerate one mismatch per that many bases
      -- None, False or 0: exact; True: 10; an int 10 .. 32 as given -- ``mismatch_per``, an int, here; without
-    ``adapters`` or ``clip``, and outside the range: ValueError."""
+    ``adapters`` or ``clip``, and outside the range: ValueError.
+    ``emit``: the reads the scan saw, as FastQ text -- None or False: off; True: handed back (``Scanner``); a path:
+    streamed there (``findseqs`` takes nothing else) -- True or the path's bytes here; ``emit_min``: the shortest read it keeps -- None:
+    the configured minreadlength, -1 here; an int >= 0 as given; anything else, and without ``emit``: ValueError (``as_emit``).  It
+    needs no profile."""
 
     def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, overrepresented=False,
-                 adapters=None, clip=None, amin=None, adapter_mismatches=None):
+                 adapters=None, clip=None, amin=None, adapter_mismatches=None, emit=None, emit_min=None):
+        self.emit, self.emit_min = as_emit(emit, emit_min)
         self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
         self.records, self.cycles, self.overrepresented = bool(records), bool(cycles), bool(overrepresented)
         self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
@@ -78,17 +110,32 @@ class ScanOptions(object):
         base = _lib.FindOpts(C.sizeof(_lib.FindOpts), flags, len(cuts), (C.c_uint8 * 8)(*cuts))
         probes = self.adapters or self.clip
         if not probes:
-            return base
+            return self._with_emit(base)
         # (the probes ride behind the 20 bytes, which stay what they are whenever the adapters and the clip are off)
         base.size, base.flags = C.sizeof(_lib.FindOptsAdapters), flags | (_lib.FIND_ADAPTERS if self.adapters else 0) | (_lib.FIND_CLIP if self.clip else 0)
         o = _lib.FindOptsAdapters(base, len(probes), (C.c_uint8 * 8)(*[len(p) for p in probes]))
         for k, p in enumerate(probes):
             C.memmove(o.probes[k], p, len(p))
         if not self.mismatch_per:
-            return o
+            return self._with_emit(o)
         # (the rate rides behind the probes, which stay what they are whenever it is off)
         o.base.size, o.base.flags = C.sizeof(_lib.FindOptsAdaptersMm), o.base.flags | _lib.FIND_ADAPTER_MISMATCHES
-        return _lib.FindOptsAdaptersMm(o, self.mismatch_per)
+        return self._with_emit(_lib.FindOptsAdaptersMm(o, self.mismatch_per))
+
+    def _with_emit(self, o):
+        """``o``, or with ``emit`` the kvq_find_opts_emit that begins with it: min_length and the path ride behind everything else, and
+        the blocks in front that ``o`` does not have stay zero (they are read only under their own flags)"""
+        if self.emit is None:
+            return o
+        if self.emit is True:
+            raise ValueError('findseqs streams the emitted reads to a file: emit= is the path of the output')
+        if isinstance(o, _lib.FindOpts):
+            o = _lib.FindOptsAdapters(o)
+        if isinstance(o, _lib.FindOptsAdapters):
+            o = _lib.FindOptsAdaptersMm(o, 0)
+        e = _lib.FindOptsEmit(o, self.emit_min, self.emit)
+        e.m.a.base.size, e.m.a.base.flags = C.sizeof(_lib.FindOptsEmit), e.m.a.base.flags | _lib.FIND_EMIT
+        return e
 
     def setters(self):
         """the kvq_scan_set_* calls of a new scan handle, in order: (name, arguments behind the handle)"""
@@ -111,4 +158,6 @@ class ScanOptions(object):
             calls.append(('kvq_scan_set_adapter_mismatches', (self.mismatch_per,)))
         if self.long_mode:
             calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
+        if self.emit is not None:
+            calls.append(('kvq_scan_set_emit', (1, self.emit_min)))      # (a path: the caller opens it and hands it over, kvq_scan_set_emit_fd)
         return calls

@@ -276,6 +276,7 @@ class Profile(object):
         self.cutoffs = list(cutoffs)
         self.adapters = adapters
         self.clipped = None                     # the ``Clip`` of a scan with ``clip=`` (set by ``profile`` and ``profile_host``)
+        self.emitted = None                     # the ``Emit`` of a scan with ``emit=`` (set by ``profile``)
         self.over = self.over_info = self.overrepresented = None
         if over is not None:
             self.over = np.array(over, dtype=np.int64)
@@ -705,6 +706,74 @@ def clip_host(text, clip, chunk_off=None, into=None, adapter_mismatches=None):
     return arr, words
 
 
+EMIT_N, EMIT_RECORDS, EMIT_EMITTED, EMIT_SHORT, EMIT_MISMATCHED, EMIT_BASES_IN, EMIT_BASES_OUT, EMIT_BYTES_OUT, EMIT_LEN = 0, 1, 2, 3, 4, 5, 6, 7, 8      # (include/kvarq_hip.h: kvq_emit_len())
+EMIT_FIELDS = ('records', 'emitted', 'short', 'mismatched', 'bases_in', 'bases_out', 'bytes_out')
+
+
+class Emit(object):
+    """what the emit of a scan wrote (kvq_scan_emit; the definition: include/kvarq_hip.h): ``records``, of them
+    ``emitted``, ``short`` (the trim left less than ``min_length``) and ``mismatched`` (bases and scores of different lengths);
+    ``bases_in`` (on all bases lines), ``bases_out`` (on the emitted ones), ``bytes_out`` (the emitted text), ``words`` (the eight
+    words) and ``min_length``, the shortest read that was kept"""
+
+    def __init__(self, words):
+        w = self.words = np.asarray(words, dtype=np.int64)
+        assert w.shape == (EMIT_LEN,)
+        self.min_length = int(w[EMIT_N])
+        for k, name in enumerate(EMIT_FIELDS):
+            setattr(self, name, int(w[EMIT_RECORDS + k]))
+
+    def __eq__(self, other):
+        return isinstance(other, Emit) and np.array_equal(self.words, other.words)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __getitem__(self, key):
+        if key not in EMIT_FIELDS + ('words',):
+            raise KeyError(key)
+        return getattr(self, key)
+
+    def line(self):
+        return 'emit: records=%d emitted=%d (%.4f) short=%d mismatched=%d bases %d -> %d bytes_out=%d min_length=%d' % (
+            self.records, self.emitted, self.emitted / float(self.records) if self.records else float('nan'), self.short, self.mismatched,
+            self.bases_in, self.bases_out, self.bytes_out, self.min_length)
+
+
+def emit_from_scan(L, h):
+    """the ``Emit`` of a finished scan object, None when the option is off"""
+    ptr = L.kvq_scan_emit(h)
+    return Emit(np.ctypeslib.as_array(ptr, shape=(EMIT_LEN,)).copy()) if ptr else None
+
+
+def emitted_from_scan(L, h):
+    """the emitted text of a finished scan object whose sink is the library's host buffer, a new uint8 array"""
+    ptr, n = C.c_void_p(), C.c_int64()
+    if L.kvq_scan_emitted(h, C.byref(ptr), C.byref(n)):
+        raise RuntimeError(_lib.last_error()[1])
+    return np.frombuffer(C.string_at(ptr.value, n.value) if n.value else b'', dtype=np.uint8)
+
+
+def emit_host(text, amin, min_length, chunk_off=None, into=None):
+    """the CPU twin of the emit (kvq_emit_host) over a text in host memory: (EMIT(text) as a new uint8 array, the eight words).
+    ``amin``: a byte value, a character or a byte; ``into``: words to add to, as the twin does.  The output buffer is exactly the
+    text's bytes plus its records long"""
+    from . import scan
+    a = amin & 0xFF if isinstance(amin, int) else (amin.encode('latin-1') if isinstance(amin, str) else bytes(amin))[0]
+    arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text)
+    co = scan.chunk_offsets(arr) if chunk_off is None else np.ascontiguousarray(chunk_off, dtype=np.int64)
+    raw = arr.tobytes()
+    nrec = sum(raw.count(b'\n', int(x), int(y)) // 4 for x, y in zip(co, co[1:]))
+    out = np.empty(arr.nbytes + nrec, dtype=np.uint8)
+    words = np.zeros(EMIT_LEN, dtype=np.int64) if into is None else into
+    n = _lib.lib().kvq_emit_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, co.ctypes.data_as(C.POINTER(C.c_int64)), len(co) - 1,
+                                 (a ^ 0x80) - 0x80, min_length, out.ctypes.data if out.nbytes else None, out.nbytes,
+                                 words.ctypes.data_as(C.POINTER(C.c_int64)))
+    if n < 0:
+        raise RuntimeError(_lib.last_error()[1])
+    return out[:n].copy(), words
+
+
 def from_scan(L, h, sources=None, adapters=None):
     """the profile of a finished scan object (kvq_scan_profile), None when it keeps none; ``sources``: as for ``Profile``;
     ``adapters``: ``(names, probes)`` of the scan's adapter probes (``ScanOptions``), which the flat array does not hold"""
@@ -799,12 +868,15 @@ def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     with the overrepresented sequences, labelled from ``sources`` (None: ``KNOWN_SOURCES``); ``adapters``: with the adapter
     content of these probes (``as_adapters``); ``clip``: of the input with the scores of its adapters masked (DESIGN section 19;
     ``Profile.clipped``: the ``Clip``); ``adapter_mismatches``: the probes of both tolerate mismatches (DESIGN section 20);
+    ``emit`` (a path) / ``emit_min``: the input's reads, trimmed (and clipped, with ``clip``), are written there as FastQ (DESIGN
+    section 21; ``Profile.emitted``: the ``Emit``) -- a BAM thereby becomes trimmed FastQ;
     ``long_reads``: as for
     ``engine.findseqs``, which takes the ``options``"""
     from . import engine
     r = engine.findseqs(fnames, [], inflate=inflate, profile=cutoffs, **options)
     p = r['profile']
     p.clipped = r.get('clip')
+    p.emitted = r.get('emit')                   # the ``Emit`` of a call with ``emit=`` (the text is in the file)
     if sources is not None and p.over is not None:
         p.relabel(sources)
     return p
@@ -826,7 +898,11 @@ def main(argv=None):
     ap.add_argument('--clip', nargs='*', metavar='NAME=SEQ', help="the profile of the input with the scores of its adapters set to '!' ahead of the trim, and how much was clipped; without arguments: the known adapters (with --adapters: the same probes)")
     ap.add_argument('--adapter-mismatches', nargs='?', type=int, const=10, default=None, metavar='PER',
                     help='with --adapters or --clip: the probes tolerate one mismatch per PER bases (10 .. 32; without a value: 10); the adapter lines gain the counts of first occurrences with 0/1/2/3 mismatches')
+    ap.add_argument('--emit', metavar='OUT', help='write the reads as the scan saw them -- cut to the quality trim at the configured Amin, behind --clip to the adapter too -- to OUT as FastQ, all files to the one output')
+    ap.add_argument('--emit-min', type=int, default=None, metavar='N', help='with --emit: keep reads of N bases and more (default: the configured minreadlength; 0 keeps every record, so that the files of two mates stay in step)')
     a = ap.parse_args(argv)
+    if a.emit_min is not None and (a.emit is None or a.emit_min < 0):
+        ap.error('--emit-min takes N >= 0 and needs --emit')
     if a.adapter_mismatches is not None and a.adapters is None and a.clip is None:
         ap.error('--adapter-mismatches needs --adapters or --clip')
     if a.adapter_mismatches is not None and not 10 <= a.adapter_mismatches <= 32:
@@ -844,6 +920,10 @@ def main(argv=None):
         more['clip'] = collections.OrderedDict((i.split('=', 1)[0], i.split('=', 1)[1].encode('latin-1')) for i in a.clip) if a.clip else True
     if a.adapter_mismatches is not None:
         more['adapter_mismatches'] = a.adapter_mismatches
+    if a.emit is not None:
+        more['emit'] = a.emit
+        if a.emit_min is not None:
+            more['emit_min'] = a.emit_min
     p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
@@ -861,6 +941,8 @@ def main(argv=None):
         print('\n'.join(p.adapter_lines()))
     if a.clip is not None:
         print(p.clipped.line())
+    if a.emit is not None:
+        print(p.emitted.line())
 
 
 if __name__ == '__main__':

@@ -92,18 +92,24 @@ class Scanner(object):
 
     def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, **options):
         self.table = table
-        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters, clip (``options.ScanOptions``), set on the
+        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters, clip, emit, emit_min (``options.ScanOptions``), set on the
         # scan handle once and kept across reset
         opt = ScanOptions(amin=bytes([table.config.Amin & 0xFF]), **options)
         self.records, self.profile, self.cycles, self.read_stats, self.long_reads = opt.records, opt.profile, opt.cycles, opt.read_stats, opt.long_reads
         self.overrepresented = opt.overrepresented
         self.adapters, self.adapter_names = opt.adapters, opt.adapter_names
         self.clip, self.clip_names = opt.clip, opt.clip_names      # (with ``clip`` the text of a batch is WRITTEN where it lies: ``scan_device``)
+        # ``emit=True``: ``finish`` hands the emitted text back ('emitted'); ``emit=<path>``: it is streamed to that file, which is
+        # created here and stays open until ``close``; ``emit_min``: the shortest read kept
+        self.emit, self.emit_min, self._emit_file = opt.emit, opt.emit_min, None
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
         for name, args in opt.setters():
             _check(getattr(_lib.lib(), name)(self.h, *args))
+        if self.emit is not None and self.emit is not True:
+            self._emit_file = open(self.emit, 'wb')
+            _check(_lib.lib().kvq_scan_set_emit_fd(self.h, self._emit_file.fileno()))
         self._host_batches = []          # copies of what scan_host was given since the last reset (fed again when the hit arena overflows)
         self._device_batches = []        # what scan_device was given since the last reset (the caller's device memory: nothing is copied)
         self._retained, self._retain_limit, self._replay = 0, (0 if replay is not None else retain_limit), replay
@@ -206,6 +212,12 @@ class Scanner(object):
             from . import profile as profile_
             out['clip'] = profile_.clip_from_scan(L, self.h, (self.clip_names, self.clip))
             out['clip_kernel_ms'] = L.kvq_scan_clip_kernel_ms(self.h)
+        if self.emit is not None:
+            from . import profile as profile_
+            out['emit'] = profile_.emit_from_scan(L, self.h)
+            out['emit_kernel_ms'] = L.kvq_scan_emit_kernel_ms(self.h)
+            if self.emit is True:
+                out['emitted'] = profile_.emitted_from_scan(L, self.h)      # the emitted FastQ text, a numpy.uint8 array
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
         out['main_kernel_ms'] = L.kvq_scan_main_kernel_ms(self.h)
         out['main_kernel_launches'] = L.kvq_scan_main_kernel_launches(self.h)
@@ -322,6 +334,9 @@ class Scanner(object):
         if self.h:
             _lib.lib().kvq_scan_destroy(self.h)
             self.h = None
+        if getattr(self, '_emit_file', None) is not None:
+            self._emit_file.close()
+            self._emit_file = None
 
     def __del__(self):
         try:
