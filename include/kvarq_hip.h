@@ -478,7 +478,7 @@ int32_t        kvq_clip_host(uint8_t *text, int64_t nbytes, const int64_t *chunk
  * kvq_scan_set_adapter_mismatches: one value per scan, for the adapter content and the clip alike; before the first batch or
  * after kvq_scan_reset, as kvq_scan_set_cycles; in any order against kvq_scan_set_adapters and kvq_scan_set_clip (it needs
  * neither, and stays while they go on and off); KVQ_ERR_RUNTIME outside {0} and [10, 32].  kvq_scan_adapter_mismatches: the
- * value.  With per > 0 the passes launch kvq_adapt_records_mm / kvq_clip_records_mm (kernels_adapt_mm.hip) in place of the exact
+ * value.  With per > 0 the passes launch kvq_adapt_records_mm / kvq_clip_records_mm (the tolerant instantiations) in place of the exact
  * kernels, and kvq_scan_adapt_kernel_ms / kvq_scan_clip_kernel_ms report whichever ran. */
 enum { KVQ_ADAPT_PER = 4, KVQ_ADAPT_B_DIST = 4, KVQ_ADAPT_DISTS = 4, KVQ_CLIP_PER = 5, KVQ_ADAPT_MIN_PER = 10, KVQ_ADAPT_MAX_PER = 32 };
 int32_t        kvq_scan_set_adapter_mismatches(kvq_scan *s, int32_t per);

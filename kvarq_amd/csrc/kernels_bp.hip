@@ -920,7 +920,7 @@ kvq_verify_survivors(KvqParams P, const uint8_t *__restrict__ data, int64_t fpos
     }
 }
 
-// kvq_trim_records' long score lines (declared in kernels_general.hip): lane l sums up scores [1024 r + 16 l, + 16) of
+// kvq_trim_records' long score lines (declared in kvq_lines.h): lane l sums up scores [1024 r + 16 l, + 16) of
 // every KiB r as a Seg (bp_runs64), an ordered tree merge over the wave gives the KiB's Seg, the KiBs are merged in turn
 __device__ void kvq_long_line_run(const uint8_t *line, uint32_t Q, int amin, int lane, int &best, uint32_t &best_start)
 {

@@ -4,6 +4,7 @@
 // an exclusive 64-bit prefix sum over those bytes (kvq_emit_block_sums, kvq_emit_scan_blocks, kvq_emit_offsets) says where, and
 // kvq_emit_copy moves the three pieces of every emitted record and writes its five fixed bytes.  The batch's text is only read.
 #include "kvq_device.h"
+#include "kvq_lines.h"
 #include "../../include/kvarq_hip.h"
 
 // what kvq_emit_size leaves per record: the class (KVQ_EMIT_CLASS_*), start and length of the trim, the bytes of its output (0: dropped)
@@ -14,44 +15,12 @@ struct KvqEmitRec { uint32_t cls, start, length, bytes; };
 // records a workgroup of the prefix sum takes (a thread each); the second level takes as many block sums a step, and carries
 #define KVQ_EMIT_SCAN_BLOCK 256u
 
-// one behind the last byte of line[0, len) that is below amin; 0: there is none (the answer in every lane) -- prof_last_low's loop
-__device__ __forceinline__ uint32_t emit_last_low(const uint8_t *line, uint32_t len, int amin, int lane)
-{
-    uint32_t last = 0;
-    for (uint32_t o = 0; o < len; o += 1024u) {
-        const uint32_t q = o + 16u * (uint32_t)lane;
-        uint32_t w[4];
-        prof_load16(line, len, q, w);
-        const uint32_t n = q < len ? (len - q < 16u ? len - q : 16u) : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; j++)
-            if (j < n && (int)(int8_t)(w[j >> 2] >> (8u * (j & 3u))) < amin) last = q + j + 1u;
-    }
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)last, d, 64); last = o > last ? o : last; }
-    return last;
-}
-
-// the engine's trim of a short score line (prof_short_load has its bytes and its newline): prof_short_trim's loop, which is
-// kvq_trim_records', with the start of the run beside its length
-template <int NG>
-__device__ __forceinline__ void emit_short_trim(const uint8_t by[NG], uint32_t qlen, int amin, int lane, int &best, uint32_t &best_start)
-{
-    RunState st; st.in_run = 1; st.run_start = 0; st.best = 0; st.best_start = 0;
-#pragma unroll
-    for (int k = 0; k < NG; k++) {
-        const uint32_t o = 64u * (uint32_t)k;
-        if (o >= qlen) break;
-        const uint64_t good = __ballot(o + (uint32_t)lane < qlen && (int)(int8_t)by[k] >= amin);
-        run_feed(st, good, (qlen - o) < 64u ? (int)(qlen - o) : 64, o);
-    }
-    best = st.best; best_start = st.best_start;
-}
-
 // Records [0, nrec) of the batch, a wave a record, KVQ_TRIM_RPW consecutive records a wave, grid-stride over waves (the shape of
-// kvq_profile_records, whose trim this is for the one cutoff amin: lines of 1024 scores and more go through kvq_long_line_run, as
-// kvq_trim_records' long score lines do).  rec[g] is written for every record.  The wave keeps its records' share of the seven
-// sums in registers (every lane the same), its first lane adds them to the workgroup's LDS, and the words that are not zero go
-// to out[1 .. 7] with one 64-bit atomic each a workgroup.
+// kvq_profile_records, whose trim this is for the one cutoff amin: the same three-way split over the helpers of kvq_lines.h.  The
+// split stands here and not in a function of its own: behind one, the compiler loads the index entry as one vector and the kernel
+// takes 100 VGPRs for 99; profiles/record_pass_refactor.txt).  rec[g] is written for every record.  The wave keeps its records'
+// share of the seven sums in registers (every lane the same), its first lane adds them to the workgroup's LDS, and the words that
+// are not zero go to out[1 .. 7] with one 64-bit atomic each a workgroup.
 extern "C" __global__ void __launch_bounds__(256)
 kvq_emit_size(const uint8_t *__restrict__ data, const uint32_t *__restrict__ nl4, const uint32_t *__restrict__ rec_start, uint32_t nrec,
               int32_t amin, uint32_t min_length, KvqEmitRec *__restrict__ rec, unsigned long long *__restrict__ out)
@@ -73,20 +42,10 @@ kvq_emit_size(const uint8_t *__restrict__ data, const uint32_t *__restrict__ nl4
             KvqEmitRec e; e.cls = KVQ_EMIT_CLASS_MISMATCHED; e.start = 0u; e.length = 0u; e.bytes = 0u;
             if (L != Q) sums[KVQ_EMIT_MISMATCHED]++;
             else {
-                int best = 0; uint32_t bstart = 0;
-                if (Q >= 1024u) {
-                    // (kvq_long_line_run closes the last run at the end of what it is given: where the newline is no low byte, the
-                    // line ends for it at its last low byte, which closes the last run that counts -- as kvq_profile_records)
-                    uint32_t end = Q; bool closed = true;
-                    if ('\n' >= amin) { const uint32_t behind = emit_last_low(sline, Q, amin, lane); closed = behind > 0u; end = behind - 1u; }
-                    if (closed) kvq_long_line_run(sline, end, amin, lane, best, bstart);
-                } else if (Q >= 256u) {
-                    uint8_t by[16]; prof_short_load<16>(sline, Q + 1u, lane, by);
-                    emit_short_trim<16>(by, Q + 1u, amin, lane, best, bstart);
-                } else {
-                    uint8_t by[4]; prof_short_load<4>(sline, Q + 1u, lane, by);
-                    emit_short_trim<4>(by, Q + 1u, amin, lane, best, bstart);
-                }
+                int best; uint32_t bstart;
+                if (Q >= 1024u) kvq_long_trim(sline, Q, amin, lane, best, bstart);
+                else if (Q >= 256u) { uint8_t by[16]; kvq_short_load<16>(sline, Q + 1u, lane, by); kvq_short_trim<16>(by, Q + 1u, amin, lane, best, bstart); }
+                else { uint8_t by[4]; kvq_short_load<4>(sline, Q + 1u, lane, by); kvq_short_trim<4>(by, Q + 1u, amin, lane, best, bstart); }
                 e.start = bstart; e.length = (uint32_t)best;
                 if ((uint32_t)best < min_length) { e.cls = KVQ_EMIT_CLASS_SHORT; sums[KVQ_EMIT_SHORT]++; }
                 else {
@@ -179,7 +138,7 @@ kvq_emit_offsets(const KvqEmitRec *__restrict__ rec, uint32_t nrec, const unsign
 // src[0, len) to dst[0, len) by the sixteen lanes of a quarter, any alignment of either.  Lane `sub` takes the 16-byte blocks sub,
 // sub + 16, ... of the DESTINATION, counted from the aligned block that holds dst[0].  The bytes of a block that lie inside the
 // piece come from one or two ALIGNED 16-byte blocks of the source, each of which holds at least one byte of the piece (the rule
-// of adapt_load16: the batch's buffer may end with its text's last byte, and an aligned block never leaves a page); they are put
+// of kvq_load16: the batch's buffer may end with its text's last byte, and an aligned block never leaves a page); they are put
 // in place with a word select and v_alignbyte.  A whole block inside the piece is one 16-byte store, an aligned word inside it one
 // dword store, the bytes of the two ragged ends go one by one: nothing is read back, no byte outside dst[0, len) is written, and
 // every byte has one lane.

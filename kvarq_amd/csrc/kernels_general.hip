@@ -11,6 +11,7 @@
 //   kvq_match_all      every read against every listed sequence, classes A/B/C (1107-1175)
 //   kvq_fold_batch     per-sequence counters, coverage/mutation fold, hit bytes (434-439, analyse.py:57-78)
 #include "kvq_device.h"
+#include "kvq_lines.h"
 
 // ---------------------------------------------------------------------------
 // newline indexing
@@ -218,39 +219,7 @@ kvq_collect_skipped(const uint8_t *__restrict__ data, const KvqSkippedTile *__re
 // quality trim
 // ---------------------------------------------------------------------------
 
-// running state of the longest-run search over the quality line, fed 64 bits
-// at a time (bit i = score byte >= Amin).  A run only counts when a low byte
-// closes it; the first of equally long runs wins (workhorse.c:1055-1068).
-struct RunState { int in_run; uint32_t run_start; int best; uint32_t best_start; };
-
-__device__ __forceinline__ void run_feed(RunState &st, uint64_t good, int nbits, uint32_t base)
-{
-    int pos = 0;
-    while (pos < nbits) {
-        if (st.in_run) {
-            const uint64_t z = (~good) >> pos;
-            const int d = z ? __ffsll((long long)z) - 1 : 64;
-            if (pos + d >= nbits) break;                       // run continues in the next word
-            const int len = (int)(base + pos + d - st.run_start);
-            if (len > st.best) { st.best = len; st.best_start = st.run_start; }
-            st.in_run = 0;
-            pos += d + 1;
-        } else {
-            const uint64_t o = good >> pos;
-            const int d = o ? __ffsll((long long)o) - 1 : 64;
-            if (pos + d >= nbits) break;
-            st.run_start = base + pos + d;
-            st.in_run = 1;
-            pos += d;
-        }
-    }
-}
-
-#define KVQ_TRIM_RPW 16   // records per wave
-// the longest run of scores >= amin among line[0 .. Q) (the byte behind it closes the last run), the first of equally long
-// ones, by all 64 lanes of a wave; the answer in every lane (kernels_bp.hip)
-__device__ void kvq_long_line_run(const uint8_t *line, uint32_t Q, int amin, int lane, int &best, uint32_t &best_start);
-
+// (RunState, run_feed, KVQ_TRIM_RPW and kvq_long_line_run: kvq_lines.h)
 // one wave per record, KVQ_TRIM_RPW consecutive records per wave.
 // read_off[g] = batch offset of the first base of the trimmed read,
 // read_len[g] = its length, or -1 when shorter than minreadlength (workhorse.c:1100)

@@ -3,8 +3,9 @@
 // those with a share of 0.1 % and more.  kvq_over_records walks the record index of the exhaustive path (kvq_index_records), as
 // the other input passes do; it reads the first 64 bytes and the last byte of every bases line, never a byte outside its record,
 // and writes nothing but the table and its state block.  kvq_over_select reads the table out.  The key and its hash are the
-// duplication's (kvq_dup_hash.h); nothing else is shared with kernels_reads.hip.
+// duplication's (kvq_dup_hash.h); beyond it and the line helpers of kvq_lines.h nothing is shared with kernels_reads.hip.
 #include "kvq_device.h"
+#include "kvq_lines.h"
 #include "kvq_dup_hash.h"
 #include "../../include/kvarq_hip.h"
 
@@ -13,40 +14,6 @@ struct KvqOverState { enum { KEYED = 0, UNKEYED = 1, WORDS = 8 }; };
 // 2^lg slots of KVQ_OVER_ROW_WORDS words each, laid out as a row of the result is: {hash, count, n, w0 .. w7}; hash 0: empty.
 // At most M keys ever go into the 4 M slots and more: a free slot is always met, and there is no overflow path
 struct KvqOverTable { unsigned long long *state, *slots; uint32_t lg; };
-
-// the sixteen bytes [q, q + 16) of a line of `len` bytes whose newline lies at line[len]: one vector where it fits into the line
-// and its newline, else words where they fit and bytes where the line ends (never a byte behind the newline); zeros behind it
-__device__ __forceinline__ void over_load16(const uint8_t *line, uint32_t len, uint32_t q, uint32_t w[4])
-{
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    if (q + 16u <= len + 1u) {
-#pragma unroll
-        for (int d = 0; d < 4; d++) __builtin_memcpy(&w[d], line + q + 4u * d, 4);
-    } else if (q < len) {
-#pragma unroll
-        for (uint32_t d = 0; d < 4u; d++) {
-            const uint32_t qd = q + 4u * d;
-            if (qd + 4u <= len + 1u) __builtin_memcpy(&w[d], line + qd, 4);
-            else {
-#pragma unroll
-                for (uint32_t j = 0; j < 4u; j++) if (qd + j < len) w[d] |= (uint32_t)line[qd + j] << (8u * j);
-            }
-        }
-    }
-}
-// the bytes of a 32-bit word that are among the first v (of the word and what follows it)
-__device__ __forceinline__ uint32_t over_keep(uint32_t v) { return v >= 4u ? 0xFFFFFFFFu : (1u << (8u * v)) - 1u; }
-
-__device__ __forceinline__ unsigned long long over_shfl64(unsigned long long v, int src)
-{
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64);
-    return (unsigned long long)hi << 32 | lo;
-}
-__device__ __forceinline__ unsigned long long over_shfl_xor64(unsigned long long v, int d)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-    return (unsigned long long)hi << 32 | lo;
-}
 
 // INSERT: `n` more copies of candidate h.  The slot from the HIGH bits of h, linear probing; *won: the caller has taken an empty
 // slot and owes it the key's length and bytes.  (The bound on the probes only keeps a broken table from hanging the device.)
@@ -112,14 +79,14 @@ kvq_over_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__ 
         const uint32_t cr = L && line[L - 1u] == '\r' ? 1u : 0u;
         const uint32_t Lk = L - cr, nkey = Lk < KVQ_DUP_KEY_BYTES ? Lk : KVQ_DUP_KEY_BYTES;
         uint32_t w[4];
-        over_load16(line, L, 16u * sub, w);
+        kvq_load16(line, L, 16u * sub, w);
         const uint32_t kv = nkey > 16u * sub ? nkey - 16u * sub : 0u;          // key bytes in this lane's piece and behind it
 #pragma unroll
-        for (uint32_t d = 0; d < 4u; d++) w[d] &= over_keep(kv > 4u * d ? kv - 4u * d : 0u);
+        for (uint32_t d = 0; d < 4u; d++) w[d] &= kvq_keep_bytes(kv > 4u * d ? kv - 4u * d : 0u);
         const unsigned long long lo = (unsigned long long)w[0] | (unsigned long long)w[1] << 32, hi = (unsigned long long)w[2] | (unsigned long long)w[3] << 32;
         unsigned long long parts = kvq_dup_word(lo, 2u * sub) ^ kvq_dup_word(hi, 2u * sub + 1u);
-        parts ^= over_shfl_xor64(parts, 1);
-        parts ^= over_shfl_xor64(parts, 2);
+        parts ^= kvq_shfl_xor64(parts, 1);
+        parts ^= kvq_shfl_xor64(parts, 2);
         const bool first = have && sub == 0u, key = first && Lk != 0u;
         const unsigned long long h = kvq_dup_close(nkey, parts);
         if (first) { if (Lk) keyed++; else unkeyed++; }
@@ -128,7 +95,7 @@ kvq_over_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__ 
         unsigned long long mult = key ? 1ull : 0ull;
         if (keys) {
             const int l0 = __ffsll((long long)keys) - 1;
-            const unsigned long long h0 = over_shfl64(h, l0);
+            const unsigned long long h0 = kvq_shfl64(h, l0);
             const unsigned long long same = __ballot(key && h == h0);
             if (same >> lane & 1ull) mult = lane == l0 ? (unsigned long long)__popcll(same) : 0ull;
         }
@@ -136,7 +103,7 @@ kvq_over_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__ 
             uint32_t won = 0; unsigned long long slot = 0;
             if (mult) slot = over_insert(T, h, mult, &won);
             won = (uint32_t)__shfl((int)won, lane & ~3, 64);
-            slot = over_shfl64(slot, lane & ~3);
+            slot = kvq_shfl64(slot, lane & ~3);
             if (won) {
                 unsigned long long *row = T.slots + slot * KVQ_OVER_ROW_WORDS;
                 if (sub == 0u) row[KVQ_OVER_ROW_N] = nkey;
@@ -183,7 +150,7 @@ kvq_over_select(KvqOverTable T, unsigned long long M, unsigned long long *__rest
         }
     }
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { cand += over_shfl_xor64(cand, d); counted += over_shfl_xor64(counted, d); }
+    for (int d = 1; d < 64; d <<= 1) { cand += kvq_shfl_xor64(cand, d); counted += kvq_shfl_xor64(counted, d); }
     if (kvq_lane() == 0 && cand) { atomicAdd(&sums[0], cand); atomicAdd(&sums[1], counted); }
     __syncthreads();
     if (threadIdx.x < 2u && sums[threadIdx.x]) atomicAdd(&out[KVQ_OVER_CANDIDATES + threadIdx.x], sums[threadIdx.x]);

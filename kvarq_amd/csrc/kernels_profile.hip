@@ -3,6 +3,7 @@
 // up to eight cutoffs.  One kernel over the record index of the exhaustive path (kvq_index_records); it reads the text
 // only inside its records and writes nothing but the profile array.
 #include "kvq_device.h"
+#include "kvq_lines.h"
 #include "../../include/kvarq_hip.h"
 
 // the cutoffs, a byte each (compared as signed char, like Amin)
@@ -41,58 +42,16 @@ __device__ __forceinline__ void prof_byte(unsigned int *bins, unsigned int *copi
     }
 }
 
-// the sixteen bytes [q, q + 16) of a line of `len` bytes whose newline lies at line[len]: one vector where it fits into the
-// line and its newline, bytes where the line ends inside it (never a byte behind the newline)
-__device__ __forceinline__ void prof_load16(const uint8_t *line, uint32_t len, uint32_t q, uint32_t w[4])
-{
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    if (q + 16u <= len + 1u) {
-#pragma unroll
-        for (int d = 0; d < 4; d++) __builtin_memcpy(&w[d], line + q + 4u * d, 4);
-    } else if (q < len) {
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; j++) if (q + j < len) w[j >> 2] |= (uint32_t)line[q + j] << (8u * (j & 3u));
-    }
-}
-
 // a line of 1024 bytes or more (a long read from BAM): a KiB a step, sixteen bytes a lane
 __device__ void prof_long_bytes(const uint8_t *line, uint32_t len, unsigned int *bins, unsigned int *copies, bool spread, int lane)
 {
     for (uint32_t o = 0; o < len; o += 1024u) {
         const uint32_t q = o + 16u * (uint32_t)lane;
         uint32_t w[4];
-        prof_load16(line, len, q, w);
+        kvq_load16(line, len, q, w);
         const uint32_t n = q < len ? (len - q < 16u ? len - q : 16u) : 0u;
 #pragma unroll
         for (uint32_t j = 0; j < 16u; j++) prof_byte(bins, copies, spread, (w[j >> 2] >> (8u * (j & 3u))) & 0xFFu, j < n, lane);
-    }
-}
-
-// one behind the last byte of line[0, len) that is below amin; 0: there is none (the answer in every lane)
-__device__ uint32_t prof_last_low(const uint8_t *line, uint32_t len, int amin, int lane)
-{
-    uint32_t last = 0;
-    for (uint32_t o = 0; o < len; o += 1024u) {
-        const uint32_t q = o + 16u * (uint32_t)lane;
-        uint32_t w[4];
-        prof_load16(line, len, q, w);
-        const uint32_t n = q < len ? (len - q < 16u ? len - q : 16u) : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; j++)
-            if (j < n && (int)(int8_t)(w[j >> 2] >> (8u * (j & 3u))) < amin) last = q + j + 1u;
-    }
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)last, d, 64); last = o > last ? o : last; }
-    return last;
-}
-
-// a line of fewer than 64 NG - 1 bytes and its newline (qlen bytes with it): lane l holds bytes l, l + 64, ...
-template <int NG>
-__device__ __forceinline__ void prof_short_load(const uint8_t *line, uint32_t qlen, int lane, uint8_t by[NG])
-{
-#pragma unroll
-    for (int k = 0; k < NG; k++) {
-        const uint32_t i = 64u * (uint32_t)k + (uint32_t)lane;
-        by[k] = line[i < qlen ? i : qlen - 1u];                    // (unconditional loads travel together; qlen >= 1: the newline)
     }
 }
 
@@ -104,22 +63,6 @@ __device__ __forceinline__ void prof_short_bytes(const uint8_t by[NG], uint32_t 
         if (64u * (uint32_t)k >= len) break;
         prof_byte(bins, copies, spread, by[k], 64u * (uint32_t)k + (uint32_t)lane < len, lane);
     }
-}
-
-// the engine's trim of a short score line at one cutoff: kvq_trim_records' loop (the line's newline is fed too: it closes
-// the last run when it is below the cutoff)
-template <int NG>
-__device__ __forceinline__ int prof_short_trim(const uint8_t by[NG], uint32_t qlen, int amin, int lane)
-{
-    RunState st; st.in_run = 1; st.run_start = 0; st.best = 0; st.best_start = 0;
-#pragma unroll
-    for (int k = 0; k < NG; k++) {
-        const uint32_t o = 64u * (uint32_t)k;
-        if (o >= qlen) break;
-        const uint64_t good = __ballot(o + (uint32_t)lane < qlen && (int)(int8_t)by[k] >= amin);
-        run_feed(st, good, (qlen - o) < 64u ? (int)(qlen - o) : 64, o);
-    }
-    return st.best;
 }
 
 // Grid-stride over waves, KVQ_TRIM_RPW consecutive records a wave (a wave a record).  prof: the profile array of
@@ -153,8 +96,8 @@ kvq_profile_records(const uint8_t *__restrict__ data, const uint32_t *__restrict
             if (lane == 0) atomicAdd(&raw[L < KVQ_PROF_RAW_BINS - 1u ? L : KVQ_PROF_RAW_BINS - 1u], 1u);
             // the bases line
             if (L >= 1024u) prof_long_bytes(bline, L, base, base_copies, spread, lane);
-            else if (L >= 256u) { uint8_t by[16]; prof_short_load<16>(bline, L + 1u, lane, by); prof_short_bytes<16>(by, L, base, base_copies, spread, lane); }
-            else { uint8_t by[4]; prof_short_load<4>(bline, L + 1u, lane, by); prof_short_bytes<4>(by, L, base, base_copies, spread, lane); }
+            else if (L >= 256u) { uint8_t by[16]; kvq_short_load<16>(bline, L + 1u, lane, by); prof_short_bytes<16>(by, L, base, base_copies, spread, lane); }
+            else { uint8_t by[4]; kvq_short_load<4>(bline, L + 1u, lane, by); prof_short_bytes<4>(by, L, base, base_copies, spread, lane); }
             // the score line, and what the trim leaves of it at every cutoff (add_rl: a read of 1024 and more in no bin)
             auto count = [&](int k, int rl) {
                 if (lane == 0) {
@@ -162,26 +105,20 @@ kvq_profile_records(const uint8_t *__restrict__ data, const uint32_t *__restrict
                     atomicMax(&sc[KvqProfLds::S_CUT_LONGEST + k], (unsigned int)rl + 1u);
                 }
             };
+            // (the split by line length stands here, over the helpers of kvq_lines.h: a short line's bytes are loaded once, for the
+            // histogram and for every cutoff)
+            int best; uint32_t start;                  // (the run the trim keeps: only its length is counted here)
             if (Q >= 1024u) {
                 prof_long_bytes(sline, Q, score, score_copies, spread, lane);
-                for (int k = 0; k < ncut; k++) {
-                    const int amin = prof_amin(C, k);
-                    // (kvq_long_line_run closes the last run at the end of what it is given: where the newline is no low
-                    // byte, the line ends for it at its last low byte, which closes the last run that counts)
-                    uint32_t end = Q; bool closed = true;
-                    if ('\n' >= amin) { const uint32_t behind = prof_last_low(sline, Q, amin, lane); closed = behind > 0u; end = behind - 1u; }
-                    int best = 0; uint32_t bstart = 0;
-                    if (closed) kvq_long_line_run(sline, end, amin, lane, best, bstart);
-                    count(k, best);
-                }
+                for (int k = 0; k < ncut; k++) { kvq_long_trim(sline, Q, prof_amin(C, k), lane, best, start); count(k, best); }
             } else if (Q >= 256u) {
-                uint8_t by[16]; prof_short_load<16>(sline, Q + 1u, lane, by);
+                uint8_t by[16]; kvq_short_load<16>(sline, Q + 1u, lane, by);
                 prof_short_bytes<16>(by, Q, score, score_copies, spread, lane);
-                for (int k = 0; k < ncut; k++) count(k, prof_short_trim<16>(by, Q + 1u, prof_amin(C, k), lane));
+                for (int k = 0; k < ncut; k++) { kvq_short_trim<16>(by, Q + 1u, prof_amin(C, k), lane, best, start); count(k, best); }
             } else {
-                uint8_t by[4]; prof_short_load<4>(sline, Q + 1u, lane, by);
+                uint8_t by[4]; kvq_short_load<4>(sline, Q + 1u, lane, by);
                 prof_short_bytes<4>(by, Q, score, score_copies, spread, lane);
-                for (int k = 0; k < ncut; k++) count(k, prof_short_trim<4>(by, Q + 1u, prof_amin(C, k), lane));
+                for (int k = 0; k < ncut; k++) { kvq_short_trim<4>(by, Q + 1u, prof_amin(C, k), lane, best, start); count(k, best); }
             }
         }
     }

@@ -4,6 +4,7 @@
 // kvq_profile_records does; it reads the text only inside its records and writes nothing but its array and the table.
 // kvq_dup_plan / kvq_dup_purge settle the table behind every slice of records, kvq_dup_levels reads it out in the tail of a scan.
 #include "kvq_device.h"
+#include "kvq_lines.h"
 #include "kvq_dup_hash.h"
 #include "../../include/kvarq_hip.h"
 
@@ -23,48 +24,20 @@ struct KvqReadsLds {
                               S_RECORDS = 613, S_GC_NONE = 614, S_MEANQ_NONE = 615, S_KEYED = 616, S_UNKEYED = 617, S_NEW = 618, WORDS = 619;
 };
 
-// the sixteen bytes [q, q + 16) of a line of `len` bytes whose newline lies at line[len]: one vector where it fits into the line
-// and its newline, else words where they fit and bytes where the line ends (never a byte behind the newline); zeros behind it
-__device__ __forceinline__ void reads_load16(const uint8_t *line, uint32_t len, uint32_t q, uint32_t w[4])
-{
-    w[0] = w[1] = w[2] = w[3] = 0u;
-    if (q + 16u <= len + 1u) {
-#pragma unroll
-        for (int d = 0; d < 4; d++) __builtin_memcpy(&w[d], line + q + 4u * d, 4);
-    } else if (q < len) {
-#pragma unroll
-        for (uint32_t d = 0; d < 4u; d++) {
-            const uint32_t qd = q + 4u * d;
-            if (qd + 4u <= len + 1u) __builtin_memcpy(&w[d], line + qd, 4);
-            else {
-#pragma unroll
-                for (uint32_t j = 0; j < 4u; j++) if (qd + j < len) w[d] |= (uint32_t)line[qd + j] << (8u * j);
-            }
-        }
-    }
-}
-
-// 0x80 in every byte of x that equals the byte repeated in c4 (exact per byte: no carry leaves a byte)
-__device__ __forceinline__ uint32_t reads_eq(uint32_t x, uint32_t c4)
-{
-    const uint32_t y = x ^ c4;
-    return ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu);
-}
 // the bytes of word d of a piece that are among its first `nvalid`
 __device__ __forceinline__ uint32_t reads_keep(uint32_t nvalid, uint32_t d)
 {
-    const uint32_t v = nvalid > 4u * d ? nvalid - 4u * d : 0u;
-    return v >= 4u ? 0xFFFFFFFFu : (1u << (8u * v)) - 1u;
+    return kvq_keep_bytes(nvalid > 4u * d ? nvalid - 4u * d : 0u);
 }
 // A C G T, G C and N among the bytes of a piece of a bases line (a zero, a newline and a '\r' are none of them)
 __device__ __forceinline__ void reads_count_bases(const uint32_t w[4], uint32_t &a, uint32_t &g, uint32_t &c)
 {
 #pragma unroll
     for (int d = 0; d < 4; d++) {
-        const uint32_t gc = reads_eq(w[d], 0x47474747u) | reads_eq(w[d], 0x43434343u);
-        a += (uint32_t)__popc(gc | reads_eq(w[d], 0x41414141u) | reads_eq(w[d], 0x54545454u));
+        const uint32_t gc = kvq_eq_flags(w[d], 0x47474747u) | kvq_eq_flags(w[d], 0x43434343u);
+        a += (uint32_t)__popc(gc | kvq_eq_flags(w[d], 0x41414141u) | kvq_eq_flags(w[d], 0x54545454u));
         g += (uint32_t)__popc(gc);
-        c += (uint32_t)__popc(reads_eq(w[d], 0x4E4E4E4Eu));
+        c += (uint32_t)__popc(kvq_eq_flags(w[d], 0x4E4E4E4Eu));
     }
 }
 // the sum of the first nvalid bytes of a piece, as unsigned
@@ -85,12 +58,6 @@ __device__ __forceinline__ unsigned long long reads_key_parts(const uint32_t w[4
     const unsigned long long lo = (unsigned long long)(w[0] & reads_keep(kv, 0)) | (unsigned long long)(w[1] & reads_keep(kv, 1)) << 32;
     const unsigned long long hi = (unsigned long long)(w[2] & reads_keep(kv, 2)) | (unsigned long long)(w[3] & reads_keep(kv, 3)) << 32;
     return kvq_dup_word(lo, 2u * sub) ^ kvq_dup_word(hi, 2u * sub + 1u);
-}
-
-__device__ __forceinline__ unsigned long long reads_shfl_xor64(unsigned long long v, int d)
-{
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-    return (unsigned long long)hi << 32 | lo;
 }
 
 // `n` more copies of key h into a table of 2^lg slots: the slot from the HIGH bits of h, linear probing.  The host's slices keep the
@@ -155,8 +122,8 @@ kvq_reads_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__
             for (uint32_t o = 0; o < top; o += 256u) {
                 const uint32_t q = o + 16u * sub;
                 uint32_t bw[4], sw[4];
-                reads_load16(bline, bl, q, bw);
-                reads_load16(sline, sl, q, sw);
+                kvq_load16(bline, bl, q, bw);
+                kvq_load16(sline, sl, q, sw);
                 reads_count_bases(bw, a, gc, c);
                 if (dup && o == 0u && sub < 4u) parts = reads_key_parts(bw, nkey, sub);
                 s32 += reads_sum(sw, q < sl ? (sl - q < 16u ? sl - q : 16u) : 0u);
@@ -165,7 +132,7 @@ kvq_reads_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__
             for (int d = 1; d < 16; d <<= 1) {
                 a += (uint32_t)__shfl_xor((int)a, d, 64); gc += (uint32_t)__shfl_xor((int)gc, d, 64); c += (uint32_t)__shfl_xor((int)c, d, 64);
                 s32 += (uint32_t)__shfl_xor((int)s32, d, 64);
-                if (dup) parts ^= reads_shfl_xor64(parts, d);
+                if (dup) parts ^= kvq_shfl_xor64(parts, d);
             }
             S = s32;
         }
@@ -183,7 +150,7 @@ kvq_reads_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__
             for (uint32_t o = 0; o < rL; o += 1024u) {
                 const uint32_t q = o + 16u * (uint32_t)lane;
                 uint32_t w[4];
-                reads_load16(bline, rL, q, w);
+                kvq_load16(bline, rL, q, w);
                 reads_count_bases(w, a2, g2, c2);
                 if (dup && o == 0u && lane < 4) p2 = reads_key_parts(w, nkey, (uint32_t)lane);
                 if (o + 1024u < o) break;                                   // (a line that ends in the last KiB below 4 GiB)
@@ -191,15 +158,15 @@ kvq_reads_records(const uint8_t *__restrict__ data, const uint32_t *__restrict__
             for (uint32_t o = 0; o < rQ; o += 1024u) {
                 const uint32_t q = o + 16u * (uint32_t)lane;
                 uint32_t w[4];
-                reads_load16(sline, rQ, q, w);
+                kvq_load16(sline, rQ, q, w);
                 S2 += reads_sum(w, q < rQ ? (rQ - q < 16u ? rQ - q : 16u) : 0u);
                 if (o + 1024u < o) break;
             }
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 a2 += (uint32_t)__shfl_xor((int)a2, d, 64); g2 += (uint32_t)__shfl_xor((int)g2, d, 64); c2 += (uint32_t)__shfl_xor((int)c2, d, 64);
-                S2 += reads_shfl_xor64(S2, d);
-                p2 ^= reads_shfl_xor64(p2, d);
+                S2 += kvq_shfl_xor64(S2, d);
+                p2 ^= kvq_shfl_xor64(p2, d);
             }
             if (quarter == (uint32_t)l >> 4) { a = a2; gc = g2; c = c2; S = S2; parts = p2; crb = cb; crs = cs; }
         }

@@ -19,6 +19,7 @@
 // This file is included by kvq_unity.hip after kernels_results.hip (KvqFinishState).
 
 #include "kvq_host.h"
+#include "kvq_lines.h"
 
 #define KVQ_REC_LANE_STEPS 32u        // aligned 16-byte blocks a lane walks alone in each direction (512 bytes)
 #define KVQ_REC_LANE_COPY 2048u       // records up to this many bytes a lane copies alone; longer ones the wave copies
@@ -79,12 +80,6 @@ __device__ int64_t kvq_rec_fwd(const uint8_t *data, int64_t n, int64_t p, int k,
     return -2;
 }
 
-__device__ __forceinline__ int64_t kvq_shfl64(int64_t v, int src)
-{
-    return (int64_t)(((unsigned long long)(unsigned int)__shfl((int)((unsigned long long)v >> 32), src, 64) << 32) |
-                     (unsigned int)__shfl((int)(unsigned int)v, src, 64));
-}
-
 // The whole wave (all lanes active, same arguments): kvq_rec_back without a step limit, 1 KiB a step.
 __device__ int64_t kvq_rec_back_wave(const uint8_t *data, int64_t lo, int64_t p, int k)
 {
@@ -108,7 +103,7 @@ __device__ int64_t kvq_rec_back_wave(const uint8_t *data, int64_t lo, int64_t p,
                 int r = k - (int)(incl - c);
                 for (;;) { const int i = 31 - __clz(m); if (--r == 0) { at = b + i; break; } m &= ~(1u << i); }
             }
-            return kvq_shfl64(at, __ffsll((long long)__ballot(here)) - 1);
+            return (int64_t)kvq_shfl64((unsigned long long)at, __ffsll((long long)__ballot(here)) - 1);
         }
         k -= (int)tot;
         if (top - 16ll * 63 <= lo) return lo - 1;
@@ -139,7 +134,7 @@ __device__ int64_t kvq_rec_fwd_wave(const uint8_t *data, int64_t n, int64_t p, i
                 int r = k - (int)(incl - c);
                 for (;;) { const int i = __ffs(m) - 1; if (--r == 0) { at = b + i; break; } m &= m - 1u; }
             }
-            return kvq_shfl64(at, __ffsll((long long)__ballot(here)) - 1);
+            return (int64_t)kvq_shfl64((unsigned long long)at, __ffsll((long long)__ballot(here)) - 1);
         }
         k -= (int)tot;
         bot += 1024;
@@ -200,7 +195,7 @@ kvq_gather_records(KvqRecTable T, const KvqHit *__restrict__ arena, uint32_t are
         }
         for (uint64_t todo = __ballot(far); todo; todo &= todo - 1ull) {
             const int w = __ffsll((long long)todo) - 1;
-            const int64_t pw = kvq_shfl64(p, w), low = kvq_shfl64(lo, w), hiw = kvq_shfl64(hi, w);
+            const int64_t pw = (int64_t)kvq_shfl64((unsigned long long)p, w), low = (int64_t)kvq_shfl64((unsigned long long)lo, w), hiw = (int64_t)kvq_shfl64((unsigned long long)hi, w);
             const int64_t a = kvq_rec_back_wave(data, low, pw, 2), e = kvq_rec_fwd_wave(data, hiw, pw, 3);
             if (lane == w) { rs = a + 1; re = e == hiw ? hiw : e + 1; }
         }
@@ -216,8 +211,8 @@ kvq_gather_records(KvqRecTable T, const KvqHit *__restrict__ arena, uint32_t are
             if (tot) base = atomicAdd(&T.ctr[0], (unsigned long long)tot);
             if (claimed) dbase = atomicAdd(&T.ctr[1], (unsigned long long)__popcll(claimed));
         }
-        base = (unsigned long long)kvq_shfl64((int64_t)base, 0);
-        dbase = (unsigned long long)kvq_shfl64((int64_t)dbase, 0);
+        base = kvq_shfl64(base, 0);
+        dbase = kvq_shfl64(dbase, 0);
         unsigned long long off = base + incl - short_len;
         if (longrec) off = atomicAdd(&T.ctr[0], (unsigned long long)len);
         const bool fits = off + len <= T.store_cap;
@@ -235,9 +230,9 @@ kvq_gather_records(KvqRecTable T, const KvqHit *__restrict__ arena, uint32_t are
         }
         for (uint64_t todo = __ballot(longrec && fits); todo; todo &= todo - 1ull) {
             const int w = __ffsll((long long)todo) - 1;
-            const uint8_t *src = data + kvq_shfl64(rs, w);
-            uint8_t *dst = T.store + (unsigned long long)kvq_shfl64((int64_t)off, w);
-            const uint64_t n = (uint64_t)kvq_shfl64((int64_t)len, w), body = n & ~15ull;
+            const uint8_t *src = data + (int64_t)kvq_shfl64((unsigned long long)rs, w);
+            uint8_t *dst = T.store + kvq_shfl64(off, w);
+            const uint64_t n = kvq_shfl64(len, w), body = n & ~15ull;
             for (uint64_t q = 16ull * (uint64_t)lane; q < body; q += 1024ull)
                 *reinterpret_cast<u32x4_any *>(dst + q) = *reinterpret_cast<const u32x4_any *>(src + q);
             if (body + (uint64_t)lane < n) dst[body + lane] = src[body + lane];

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <string>
 #include <unistd.h>
 #include <utility>
@@ -155,6 +156,19 @@ struct KvqPass {
     std::vector<KvqEventPair> ev; double ms = 0;        // around the pass's kernels of every batch; their sum
 };
 
+// the probes of an adapter option as the caller gave them: n of them (0: the option is off), their lengths and bytes; what is
+// not in use is zero
+struct KvqProbeSet {
+    int32_t n = 0; uint8_t lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
+    void clear() { *this = KvqProbeSet(); }
+    void assign(const uint8_t *const *p, const int32_t *l, int32_t count)
+    {
+        clear();
+        n = count;
+        for (int32_t k = 0; k < n; k++) { lens[k] = (uint8_t)l[k]; memcpy(probes[k], p[k], (size_t)l[k]); }
+    }
+};
+
 struct kvq_scan {
     const kvq_table *t = nullptr;
     kvq_comm *comm = nullptr;            // several GPUs: `finish` sums the counters of all ranks over it (kvq_dist.hip)
@@ -251,10 +265,9 @@ struct kvq_scan {
     // the overrepresented sequences: M, the slots of the table (the pass's array: KvqOverLayout), and the records the pass has seen
     // since it was last cleared -- the first M of them make the candidates
     uint64_t over_M = 0, over_slots = 0, over_seen = 0;
-    // the adapter content: the probes (kvq_scan_set_adapters; adapt_n == 0: off)
-    int32_t adapt_n = 0; uint8_t adapt_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t adapt_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
-    // the adapter clip (kvq_scan_set_clip): its probes (clip_n == 0: off); its array is passes[KVQ_PASS_CLIP]
-    int32_t clip_n = 0; uint8_t clip_lens[KVQ_ADAPT_MAX_PROBES] = { 0 }; uint8_t clip_probes[KVQ_ADAPT_MAX_PROBES][KVQ_ADAPT_MAX_PROBE] = { { 0 } };
+    // the probes of the adapter content (kvq_scan_set_adapters) and of the adapter clip (kvq_scan_set_clip; its
+    // array is passes[KVQ_PASS_CLIP]); n == 0: off
+    KvqProbeSet adapt, clip;
     // one mismatch per this many bases in the probes of both (kvq_scan_set_adapter_mismatches): 0, the exact rule, or 10 .. 32
     int32_t adapt_per = 0;
     // the emit (kvq_scan_set_emit): its words are passes[KVQ_PASS_EMIT] (the array has the batch's total and the copies of

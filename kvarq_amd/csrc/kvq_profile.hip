@@ -2,6 +2,7 @@
 // per-cycle counts, the per-read statistics, the overrepresented sequences, the adapter content and the adapter clip (section 19), with the mismatch rate of their probes (section 20), and the emit of the trimmed reads (section 21), as options of a scan object, the steps of their common lifecycle, the launch of
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
+#include "kvq_lines.h"
 #include <array>
 #include <string.h>
 #include <sys/stat.h>
@@ -79,7 +80,7 @@ static void over_off(kvq_scan *s)
 
 static void adapt_off(kvq_scan *s)
 {
-    s->adapt_n = 0;
+    s->adapt.clear();
     pass_off(s, s->passes[KVQ_PASS_ADAPT]);
 }
 
@@ -154,13 +155,13 @@ static void passes_landed(kvq_scan *s)
     if (s->passes[KVQ_PASS_ADAPT].on) {
         // the words that are no sums: n and every m_k
         std::vector<int64_t> &h = s->passes[KVQ_PASS_ADAPT].h;
-        h[KVQ_ADAPT_N] = s->adapt_n;
+        h[KVQ_ADAPT_N] = s->adapt.n;
         if (s->adapt_per) h[KVQ_ADAPT_PER] = s->adapt_per;
-        for (int k = 0; k < s->adapt_n; k++) h[KVQ_ADAPT_BLOCKS + (size_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = s->adapt_lens[k];
+        for (int k = 0; k < s->adapt.n; k++) h[KVQ_ADAPT_BLOCKS + (size_t)k * KVQ_ADAPT_BLOCK_WORDS + KVQ_ADAPT_B_M] = s->adapt.lens[k];
     }
     if (s->passes[KVQ_PASS_CLIP].on) {
         // the words that are no sums: n and per
-        s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_N] = s->clip_n;
+        s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_N] = s->clip.n;
         if (s->adapt_per) s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_PER] = s->adapt_per;
     }
     if (s->passes[KVQ_PASS_EMIT].on) s->passes[KVQ_PASS_EMIT].h[KVQ_EMIT_N] = s->emit_min;      // (the word that is no sum)
@@ -393,20 +394,18 @@ extern "C" int32_t kvq_scan_set_adapters(kvq_scan *s, const uint8_t *const *prob
     }
     if (!adapt_probes_ok("kvq_scan_set_adapters", probes, lens, n)) return KVQ_ERR_RUNTIME;
     if ((rc = pass_make(s->passes[KVQ_PASS_ADAPT], (size_t)KVQ_ADAPT_WORDS * 8, KVQ_ADAPT_WORDS, (size_t)KVQ_ADAPT_WORDS * 8))) { adapt_off(s); return rc; }
-    s->adapt_n = n;
-    memset(s->adapt_lens, 0, sizeof(s->adapt_lens)); memset(s->adapt_probes, 0, sizeof(s->adapt_probes));
-    for (int32_t k = 0; k < n; k++) { s->adapt_lens[k] = (uint8_t)lens[k]; memcpy(s->adapt_probes[k], probes[k], (size_t)lens[k]); }
+    s->adapt.assign(probes, lens, n);
     return pass_clear(s, KVQ_PASS_ADAPT);
 }
 
-// n probes as the kernels take them, by value: 2-bit codes, masks and lengths (kvq_adapt_records and kvq_clip_records)
-static KvqAdaptProbes adapt_probes(int32_t n, const uint8_t *lens, const uint8_t (*probes)[KVQ_ADAPT_MAX_PROBE])
+// a probe set as the exact search takes it, by value: 2-bit codes, masks and lengths
+static KvqAdaptProbes adapt_probes(const KvqProbeSet &S)
 {
     KvqAdaptProbes P; memset(&P, 0, sizeof(P));
-    P.n = (uint32_t)n;
-    for (int k = 0; k < n; k++) {
-        const uint32_t m = lens[k];
-        for (uint32_t i = 0; i < m; i++) P.code[k] |= (unsigned long long)((probes[k][i] >> 1) & 3u) << (2u * i);
+    P.n = (uint32_t)S.n;
+    for (int k = 0; k < S.n; k++) {
+        const uint32_t m = S.lens[k];
+        for (uint32_t i = 0; i < m; i++) P.code[k] |= (unsigned long long)((S.probes[k][i] >> 1) & 3u) << (2u * i);
         P.mask[k] = m >= 32u ? ~0ull : (1ull << (2u * m)) - 1ull;               // (no shift by 64)
         P.m[k] = m;
     }
@@ -425,39 +424,34 @@ extern "C" int32_t kvq_scan_set_adapter_mismatches(kvq_scan *s, int32_t per)
 }
 extern "C" int32_t kvq_scan_adapter_mismatches(const kvq_scan *s) { return s->adapt_per; }
 
-// n probes as the tolerant kernels take them, by value: two planes of one bit a base, masks, lengths and budgets
-// (kvq_adapt_records_mm and kvq_clip_records_mm)
-static KvqAdaptProbesMm adapt_probes_mm(int32_t n, const uint8_t *lens, const uint8_t (*probes)[KVQ_ADAPT_MAX_PROBE], int32_t per)
+// a probe set as the tolerant search takes it, by value: two planes of one bit a base, masks, lengths and budgets
+static KvqAdaptProbesMm adapt_probes_mm(const KvqProbeSet &S, int32_t per)
 {
     KvqAdaptProbesMm P; memset(&P, 0, sizeof(P));
-    P.n = (uint32_t)n; P.per = (uint32_t)per;
-    for (int k = 0; k < n; k++) {
-        const uint32_t m = lens[k];
-        for (uint32_t i = 0; i < m; i++) { P.lo[k] |= (uint32_t)((probes[k][i] >> 1) & 1u) << i; P.hi[k] |= (uint32_t)((probes[k][i] >> 2) & 1u) << i; }
+    P.n = (uint32_t)S.n; P.per = (uint32_t)per;
+    for (int k = 0; k < S.n; k++) {
+        const uint32_t m = S.lens[k];
+        for (uint32_t i = 0; i < m; i++) { P.lo[k] |= (uint32_t)((S.probes[k][i] >> 1) & 1u) << i; P.hi[k] |= (uint32_t)((S.probes[k][i] >> 2) & 1u) << i; }
         P.mask[k] = m >= 32u ? ~0u : (1u << m) - 1u;                            // (no shift by 32)
         P.m[k] = m; P.e[k] = m / (uint32_t)per;
     }
     return P;
 }
 
-// the pass over the R records of a batch, behind its other passes: the probes go along by value, as 2-bit codes; with a mismatch
-// rate, the tolerant kernel in place of the exact one
-static int adapt_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
+// the pass over the R records of a batch, behind its other passes: the probes go along by value; with a mismatch rate, the
+// instantiation for the tolerant probes in place of the one for the exact ones
+template <class Probes> static int adapt_launch(kvq_scan *s, const uint8_t *d_data, uint64_t R, const Probes &P)
 {
-    if (R == 0) return KVQ_OK;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
-    if (s->adapt_per > 0) {
-        const KvqAdaptProbesMm P = adapt_probes_mm(s->adapt_n, s->adapt_lens, s->adapt_probes, s->adapt_per);
-        hipLaunchKernelGGL(kvq_adapt_mm_kernel(P.n), dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
-                           (uint32_t)R, P, s->passes[KVQ_PASS_ADAPT].d.as<unsigned long long>());
-        KVQ_HIP(hipGetLastError());
-        return KVQ_OK;
-    }
-    const KvqAdaptProbes P = adapt_probes(s->adapt_n, s->adapt_lens, s->adapt_probes);
-    hipLaunchKernelGGL(kvq_adapt_kernel(P.n), dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
+    hipLaunchKernelGGL(kvq_probe_kernels<Probes>(P.n).adapt, dim3(grid), dim3(256), (size_t)KvqAdaptLds::words(P.n) * 4, s->stream, d_data, s->d_nl4.as<uint32_t>(),
                        (uint32_t)R, P, s->passes[KVQ_PASS_ADAPT].d.as<unsigned long long>());
     KVQ_HIP(hipGetLastError());
     return KVQ_OK;
+}
+static int adapt_enqueue(kvq_scan *s, const uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    return s->adapt_per > 0 ? adapt_launch(s, d_data, R, adapt_probes_mm(s->adapt, s->adapt_per)) : adapt_launch(s, d_data, R, adapt_probes(s->adapt));
 }
 
 extern "C" const int64_t *kvq_scan_adapters(const kvq_scan *s) { return pass_result(s, KVQ_PASS_ADAPT); }
@@ -469,7 +463,7 @@ extern "C" int64_t kvq_clip_len(void) { return KVQ_CLIP_WORDS; }
 
 static void clip_off(kvq_scan *s)
 {
-    s->clip_n = 0;
+    s->clip.clear();
     pass_off(s, s->passes[KVQ_PASS_CLIP]);
 }
 
@@ -485,29 +479,23 @@ extern "C" int32_t kvq_scan_set_clip(kvq_scan *s, const uint8_t *const *probes, 
         return KVQ_ERR_RUNTIME;
     }
     if ((rc = pass_make(s->passes[KVQ_PASS_CLIP], (size_t)KVQ_CLIP_WORDS * 8, KVQ_CLIP_WORDS, (size_t)KVQ_CLIP_WORDS * 8))) { clip_off(s); return rc; }
-    s->clip_n = n;
-    memset(s->clip_lens, 0, sizeof(s->clip_lens)); memset(s->clip_probes, 0, sizeof(s->clip_probes));
-    for (int32_t k = 0; k < n; k++) { s->clip_lens[k] = (uint8_t)lens[k]; memcpy(s->clip_probes[k], probes[k], (size_t)lens[k]); }
+    s->clip.assign(probes, lens, n);
     return pass_clear(s, KVQ_PASS_CLIP);
 }
 
 // the clip over the R records of a batch whose index is on the scan's stream, in front of its scan: the text at d_data is written
-static int clip_enqueue(kvq_scan *s, uint8_t *d_data, uint64_t R)
+template <class Probes> static int clip_launch(kvq_scan *s, uint8_t *d_data, uint64_t R, const Probes &P)
 {
-    if (R == 0) return KVQ_OK;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((R + 15) / 16, 2048);               // (the kernel strides over what there is)
-    if (s->adapt_per > 0) {
-        const KvqAdaptProbesMm P = adapt_probes_mm(s->clip_n, s->clip_lens, s->clip_probes, s->adapt_per);
-        hipLaunchKernelGGL(kvq_clip_mm_kernel(P.n), dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, P,
-                           s->passes[KVQ_PASS_CLIP].d.as<unsigned long long>());
-        KVQ_HIP(hipGetLastError());
-        return KVQ_OK;
-    }
-    const KvqAdaptProbes P = adapt_probes(s->clip_n, s->clip_lens, s->clip_probes);
-    hipLaunchKernelGGL(kvq_clip_kernel(P.n), dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, P,
+    hipLaunchKernelGGL(kvq_probe_kernels<Probes>(P.n).clip, dim3(grid), dim3(256), 0, s->stream, d_data, s->d_nl4.as<uint32_t>(), (uint32_t)R, P,
                        s->passes[KVQ_PASS_CLIP].d.as<unsigned long long>());
     KVQ_HIP(hipGetLastError());
     return KVQ_OK;
+}
+static int clip_enqueue(kvq_scan *s, uint8_t *d_data, uint64_t R)
+{
+    if (R == 0) return KVQ_OK;
+    return s->adapt_per > 0 ? clip_launch(s, d_data, R, adapt_probes_mm(s->clip, s->adapt_per)) : clip_launch(s, d_data, R, adapt_probes(s->clip));
 }
 
 extern "C" const int64_t *kvq_scan_clip(const kvq_scan *s) { return pass_result(s, KVQ_PASS_CLIP); }

@@ -1,6 +1,7 @@
 // kvarq_amd/csrc/kvq_scan.hip -- the scan object and the life of a batch: create / reset / destroy, the chain of the persistent kernels,
 // run_batch (the kernels of one batch, in named steps), the one whole-batch redo, and the ways a batch comes in (device, host, staged)
 #include "kvq_host.h"
+#include "kvq_lines.h"
 #include <algorithm>
 #include <atomic>
 #include <mutex>
@@ -441,10 +442,10 @@ static int exhaustive_pass(kvq_scan *s, BatchRun &B, const int32_t *d_exh, int32
     const uint64_t R = (uint64_t)B.nrec;
     if (R == 0) return KVQ_OK;
     if ((rc = s->d_read_off.ensure((size_t)R * 4)) || (rc = s->d_read_len.ensure((size_t)R * 4))) return rc;
-    const uint32_t per_block = 4 * 16;       // KVQ_TRIM_RPW records per wave
+    const uint32_t per_block = 4 * KVQ_TRIM_RPW;
     hipLaunchKernelGGL(kvq_trim_records, dim3((uint32_t)((R + per_block - 1) / per_block)), dim3(256), 0, s->stream, B.P, d_data,
                        B.fpos_base, (uint32_t)R, KvqDevCount{ nullptr, 0, 0, nullptr }, s->d_nl4.as<uint32_t>(), s->d_rec_start.as<uint32_t>(),
-                       s->d_read_off.as<uint32_t>(), s->d_read_len.as<int32_t>(), hist_done ? 0 : 1, 16u, (unsigned int *)nullptr, 0u);
+                       s->d_read_off.as<uint32_t>(), s->d_read_len.as<int32_t>(), hist_done ? 0 : 1, (uint32_t)KVQ_TRIM_RPW, (unsigned int *)nullptr, 0u);
     if (n_exh > 0) {
         const bool main_here = !B.use_seeded && !B.read_list;     // (the read-list route's main kernel is kvq_seed_list)
         if (main_here) { if ((rc = new_event_pair(s, s->ev_main))) return rc; KVQ_HIP(hipEventRecord(s->ev_main.back().first, s->stream)); }
@@ -555,7 +556,7 @@ static int run_batch(kvq_scan *s, size_t batch_no, const uint8_t *d_data, bool e
     if ((rc = chunk_table(s, B, b.chunk_off.data()))) return rc;
     if ((rc = new_event_pair(s, s->ev_all))) return rc;
     KVQ_HIP(hipEventRecord(s->ev_all.back().first, s->stream));
-    if (s->clip_n && !exhaustive_only && (rc = clip_text(s, B))) return rc;
+    if (s->clip.n && !exhaustive_only && (rc = clip_text(s, B))) return rc;
 
     if (B.use_seeded) {
         if ((rc = new_event_pair(s, s->ev_main))) return rc;
