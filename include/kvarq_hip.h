@@ -541,6 +541,53 @@ double         kvq_scan_emit_kernel_ms(const kvq_scan *s);   /* GPU time of kvq_
 int64_t        kvq_emit_host(const uint8_t *text, int64_t nbytes, const int64_t *chunk_off, int64_t nchunks, int32_t amin, int32_t min_length,
                              uint8_t *out_text, int64_t out_cap, int64_t *out_words);
 
+/* ---- the emitted reads, deflated to BGZF on the device: THE OUTPUT IS A FUNCTION OF THE TEXT ALONE ----
+ * BGZF(text), for the emitted text of one batch: the text is cut into blocks of 65 280 bytes (bgzip's 0xff00), the last one
+ * shorter; an empty text gives no member.  Each block is one BGZF member: the 18-byte header with the 'BC' subfield and BSIZE,
+ * one raw DEFLATE stream of one final block, the CRC-32 of the block's bytes, ISIZE.  The stream is a dynamic-Huffman block
+ * (BTYPE 2) over the LZ77 parse below, or, where that is no shorter, a stored block (BTYPE 0: 65 280 + 5 + 26 bytes at most,
+ * inside the 65 536 a member may have).  There is no fixed-Huffman block.
+ * THE PARSE (kvq_deflate.h states it in running code, for the twin and the kernel alike): a block is cut into 256 segments of 255
+ * bytes.  A segment is parsed greedily from its first byte and needs nothing of the parse of another.  Every segment has a table
+ * of 128 slots that maps the hash of three bytes to the last position of the segment that has it, every position entered; the
+ * parse of segment s keeps its own table for the positions in front of the current one and looks into the FINAL tables of
+ * segments s - 1 and s - 2.  A candidate's match is the common prefix of the raw block at both places, cut at the segment's end:
+ * length 3 .. 255, distance 1 .. 762 (a match begins at 252 of its segment at the latest, against the first byte of segment s - 2); the longest wins, the nearest table among equals; below three bytes the byte is a literal.
+ * THE CODES: Huffman lengths limited to 15 (7 for the code-length code) by kvq_deflate_lengths, canonical codes, the header's
+ * lengths run-length coded by one greedy rule; a block without a match states one distance code of one bit.
+ * Launch geometry, timing and the order of atomics change nothing: the GPU's bytes are the twin's bytes.
+ * THE WORDS, kvq_deflate_len() = 8 of them, all sums over the members but the two maxima:
+ *   [0] members   [1] bytes in   [2] bytes out (without the EOF member)   [3] members that fell back to stored
+ *   [4] match tokens   [5] literal tokens   [6] the longest distance   [7] the longest match -- of the members that are not stored
+ * kvq_scan_set_emit_compress(s, on): the emitted text of every batch reaches the sink as BGZF(text); it needs the emit on and
+ * the scan idle, and takes the refusals kvq_scan_set_emit_fd takes.  When the scan finishes the sink gets the 28-byte EOF member
+ * (kvq_bgzf_eof), once: a scan that emitted nothing yields the EOF member alone, a valid empty gzip.  The words and the EOF
+ * flag are cleared where the sink is, so a replay after an arena overflow still leaves one stream with one EOF member.  The
+ * uncompressed text never leaves the device; the eight emit words, the guards and every result are what they are without it;
+ * [1] equals the emit's word [7].  Every batch waits on the host once more, for its compressed byte count.  Off (the default),
+ * nothing is enqueued, allocated or changed.  kvq_scan_emitted then hands out the compressed bytes.
+ * kvq_scan_emit_compress: the words (valid after kvq_scan_finish until the next reset), NULL when the option is off.
+ * kvq_deflate_bgzf_device: BGZF(d_text[0, nbytes)) into d_out[0, out_cap), both device memory; returns its length or -1 (bad
+ * arguments, a device error, out_cap below the length: no byte at or behind out_cap is then written); kvq_deflate_bound(nbytes)
+ * always holds it.  No byte behind the length is written.  Sets out_words.  Blocking.
+ * kvq_deflate_bgzf_host: the CPU twin over the same definition, test infrastructure and not a fallback; same arguments in host memory.
+ * kvq_deflate_lengths_host: the length-limited code builder on its own: lens[0, nsym) for freq[0, nsym), nsym <= 288, limit 1 .. 15;
+ * more used symbols than 2^limit, counts that sum to 2^32 or more (the tree's weights are 32-bit), and anything else out of range:
+ * KVQ_ERR_RUNTIME.
+ * Environment, read at every deflate (for tests): KVQ_DEFLATE_ROUND=<members> lets fewer than 2048 members go through their
+ * slots at a time, so that a small text takes several rounds; the output does not depend on it. */
+enum { KVQ_DEFLATE_MEMBERS = 0, KVQ_DEFLATE_BYTES_IN = 1, KVQ_DEFLATE_BYTES_OUT = 2, KVQ_DEFLATE_STORED = 3, KVQ_DEFLATE_MATCHES = 4,
+       KVQ_DEFLATE_LITERALS = 5, KVQ_DEFLATE_MAX_DISTANCE = 6, KVQ_DEFLATE_MAX_LENGTH = 7, KVQ_DEFLATE_WORDS = 8 };
+int64_t        kvq_deflate_len(void);
+int64_t        kvq_deflate_bound(int64_t nbytes);
+const uint8_t *kvq_bgzf_eof(void);                           /* the 28 bytes */
+int32_t        kvq_scan_set_emit_compress(kvq_scan *s, int32_t on);
+const int64_t *kvq_scan_emit_compress(const kvq_scan *s);
+double         kvq_scan_emit_deflate_kernel_ms(const kvq_scan *s);   /* GPU time of the deflate's kernels (0 when the option is off) */
+int64_t        kvq_deflate_bgzf_device(const void *d_text, int64_t nbytes, void *d_out, int64_t out_cap, int64_t *out_words);
+int64_t        kvq_deflate_bgzf_host(const uint8_t *text, int64_t nbytes, uint8_t *out, int64_t out_cap, int64_t *out_words);
+int32_t        kvq_deflate_lengths_host(const uint32_t *freq, int32_t nsym, int32_t limit, uint8_t *lens);
+
 /* GPU time of all scan kernels enqueued so far on this scan's stream, from HIP
  * events around the launches (valid after kvq_scan_finish); and the same for
  * the dominant (read-scanning) kernel alone plus its launch count */
@@ -784,6 +831,10 @@ typedef struct kvq_find_opts_emit {
     int32_t  min_length;
     const char *path;
 } kvq_find_opts_emit;
+/* KVQ_FIND_EMIT_BGZF: kvq_scan_set_emit_compress(1) for the call: the file is BGZF, its EOF member written
+ * before the descriptor is closed.  It is read only with KVQ_FIND_EMIT, and without it the call is KVQ_ERR_RUNTIME.  It needs
+ * no structure of its own. */
+#define KVQ_FIND_EMIT_BGZF 16384u
 kvq_scan *kvq_findseqs_opts(const char *const *files, int32_t nfiles,
                             const uint8_t *const *seqs, const int32_t *seqlens, int32_t nseq, const kvq_find_opts *opts);
 

@@ -22,6 +22,7 @@ FIND_ADAPTERS = 1024                                             # ... the adapt
 FIND_CLIP = 2048                                                 # ... the adapter clip ahead of the trim (no profile needed; the same probe block)
 FIND_ADAPTER_MISMATCHES = 4096                                   # ... the probes of both tolerate mismatches (the rate in FindOptsAdaptersMm)
 FIND_EMIT = 8192                                                 # ... the trimmed reads as FastQ text (min_length and the output's path in FindOptsEmit)
+FIND_EMIT_BGZF = 16384                                           # ... deflated to BGZF on the device (read only with FIND_EMIT)
 READ_STATS, READ_DUPLICATION = 1, 2                           # kvq_scan_set_read_stats
 FIND_LONG_READS, FIND_LONG_READS_AUTO = 32, 64                   # kvq_findseqs_ex / _opts: the read-list route, always / by the batch's head
 LONG_READS_MODES = {False: 0, True: 1, 'auto': 2}                # kvq_scan_set_long_reads
@@ -179,6 +180,15 @@ PROTOTYPES = {
     'kvq_scan_emit_guard': (i64, [vp]),
     'kvq_scan_emit_kernel_ms': (C.c_double, [vp]),
     'kvq_emit_host': (i64, [vp, i64, P(i64), i64, i32, i32, vp, i64, P(i64)]),
+    'kvq_deflate_len': (i64, []),
+    'kvq_deflate_bound': (i64, [i64]),
+    'kvq_bgzf_eof': (vp, []),
+    'kvq_scan_set_emit_compress': (i32, [vp, i32]),
+    'kvq_scan_emit_compress': (P(i64), [vp]),
+    'kvq_scan_emit_deflate_kernel_ms': (C.c_double, [vp]),
+    'kvq_deflate_bgzf_device': (i64, [vp, i64, vp, i64, P(i64)]),
+    'kvq_deflate_bgzf_host': (i64, [vp, i64, vp, i64, P(i64)]),
+    'kvq_deflate_lengths_host': (i32, [vp, i32, i32, vp]),
     'kvq_scan_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_main_kernel_ms': (C.c_double, [vp]),
     'kvq_scan_profile_kernel_ms': (C.c_double, [vp]),

@@ -48,6 +48,7 @@ class Analyser(object):
         self.profile = None                     # the profile of the input, when ``scan`` took one (profile=<cutoffs>)
         self.clip = None                        # what the adapter clip did, when ``scan`` clipped (clip=<probes>): a ``profile.Clip``
         self.emit = None                        # what the emit wrote, when ``scan`` emitted the trimmed reads (emit=<path>): a ``profile.Emit``
+        self.emit_compress = None               # what its deflate did, with ``emit_compress=True``: the dict of ``profile.deflate_words``
         self.results = {}                       # testsuite interpretation is out of scope: stays empty
         self.scantime = -1
 
@@ -76,7 +77,7 @@ class Analyser(object):
         duplication (``info['profile']['per_read']`` / ``['duplication']``), ``overrepresented=True`` the overrepresented
         sequences (``info['profile']['overrepresented']``), ``adapters=`` the adapter content (``info['profile']['adapters']``); ``clip=`` masks the
         scores of adapters ahead of the trim and keeps what it did in ``self.clip``; ``adapter_mismatches=`` lets the probes of both tolerate mismatches; ``emit=<path>`` (with ``emit_min=``) writes
-        the trimmed reads there as FastQ and keeps what it wrote in ``self.emit``; ``long_reads``: as for ``engine.findseqs``,
+        the trimmed reads there as FastQ and keeps what it wrote in ``self.emit`` (``emit_compress=True``: as BGZF, deflated on the GPU; ``self.emit_compress``); ``long_reads``: as for ``engine.findseqs``,
         which takes all of them."""
         self.fastq = fastq
         self.fastq_filenames = fastq.filenames()
@@ -96,6 +97,7 @@ class Analyser(object):
         self.profile = ret.get('profile')
         self.clip = ret.get('clip')
         self.emit = ret.get('emit')
+        self.emit_compress = ret.get('emit_compress')
         self.scantime = time.time() - t0
         self.update_coverages()
 

@@ -225,6 +225,10 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
         emit_min = ((const kvq_find_opts_emit *)opts)->min_length; emit_path = ((const kvq_find_opts_emit *)opts)->path;
         if (!emit_path || !emit_path[0]) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_EMIT needs the path of the output"); return nullptr; }
     }
+    if ((flags & KVQ_FIND_EMIT_BGZF) && !(flags & KVQ_FIND_EMIT)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_findseqs_opts: KVQ_FIND_EMIT_BGZF needs KVQ_FIND_EMIT (it is the form of its output)");
+        return nullptr;
+    }
     int expected = 0;
     if (!g_running.compare_exchange_strong(expected, 1)) {            // workhorse.c:1258-1263
         kvq_set_error(KVQ_ERR_RUNTIME, "findseqs() already running!");
@@ -266,7 +270,8 @@ static kvq_scan *findseqs_impl(const char *const *files, int32_t nfiles,
               kvq_scan_set_adapters(s, probes, probe_lens, (flags & KVQ_FIND_ADAPTERS) ? nprobes : 0) ||
               kvq_scan_set_clip(s, probes, probe_lens, (flags & KVQ_FIND_CLIP) ? nprobes : 0) ||
               kvq_scan_set_adapter_mismatches(s, mismatch_per) ||
-              kvq_scan_set_emit(s, (flags & KVQ_FIND_EMIT) ? 1 : 0, emit_min))) {
+              kvq_scan_set_emit(s, (flags & KVQ_FIND_EMIT) ? 1 : 0, emit_min) ||
+              ((flags & KVQ_FIND_EMIT) && kvq_scan_set_emit_compress(s, (flags & KVQ_FIND_EMIT_BGZF) ? 1 : 0)))) {
         kvq_scan_destroy(s); kvq_table_destroy(t); s = nullptr; t = nullptr;
     }
     // the one output of KVQ_FIND_EMIT: every file of the call goes to it, in order (a rescan after an arena overflow empties it: pass_clear)

@@ -285,7 +285,7 @@ static int finish_once(kvq_scan *s)
         }
         if (s->records_on && (rc = records_fetch(s, n_hits, rec_used))) return rc;
         memcpy(s->h_ctr.data(), s->pin, (size_t)t->ctr_len * 8);
-        passes_landed(s);
+        if ((rc = passes_landed(s))) return rc;
         s->pin_res = s->pin + ctr_b;
         if (!n_hits) memset(s->pin_res + L.hitseq_off, 0, 8);
         s->res = L; s->n_hits = n_hits;

@@ -156,6 +156,12 @@ struct KvqPass {
     std::vector<KvqEventPair> ev; double ms = 0;        // around the pass's kernels of every batch; their sum
 };
 
+// the device buffers of a deflate (kernels_deflate.hip): the slots of a round's members, their sizes (which become
+// their offsets) and lengths, the tokens of the workgroups of the grid, the words
+struct KvqDeflateBufs { DevBuf slots, sizes, lens, tokens, words; };
+int  kvq_deflate_enqueue(const uint8_t *d_text, uint64_t nbytes, uint8_t *d_out, uint64_t cap, KvqDeflateBufs &B, hipStream_t stream);
+void kvq_deflate_release(KvqDeflateBufs &B);
+
 // the probes of an adapter option as the caller gave them: n of them (0: the option is off), their lengths and bytes; what is
 // not in use is zero
 struct KvqProbeSet {
@@ -280,6 +286,14 @@ struct kvq_scan {
     hipEvent_t emit_ev[2] = { nullptr, nullptr };
     std::vector<uint8_t> emit_sink; int emit_fd = -1;
     int64_t emit_guard_bad = 0;
+    // the emit's deflate (kvq_scan_set_emit_compress): on, every batch's text goes through kvq_deflate_enqueue into
+    // d_deflate_out and that stream takes the text's way through the two halves; the words of the batches so far (summed on the host:
+    // every batch lands its own in deflate_pin), whether the sink has its EOF member, the event pairs around the batches' kernels
+    bool emit_compress = false, emit_eof_done = false;
+    KvqDeflateBufs deflate; DevBuf d_deflate_out;
+    int64_t *deflate_pin = nullptr; size_t deflate_pin_cap = 0;
+    int64_t deflate_words[KVQ_DEFLATE_WORDS] = { 0 };
+    std::vector<KvqEventPair> deflate_ev; size_t deflate_ev_n = 0;
 };
 
 // kvq_scan.hip: KVQ_OK while the scan holds no batch -- the one moment at which the setter `who` may change an option -- else its refusal

@@ -3,6 +3,7 @@
 // each pass behind a batch's kernels and its way to the host in the tail of a scan (their CPU twins: kvq_twins.cpp)
 #include "kvq_host.h"
 #include "kvq_lines.h"
+#include "kvq_deflate.h"
 #include <array>
 #include <string.h>
 #include <sys/stat.h>
@@ -95,6 +96,9 @@ static int pass_clear(kvq_scan *s, int which)
     if (which == KVQ_PASS_EMIT) {
         // the sink is empty again: a batch that runs again is emitted once (no batch is in flight here: every batch's emit ends with a host wait)
         s->emit_sink.clear(); s->emit_guard_bad = 0;
+        // (and with it the deflate's words and its EOF member: a replay still leaves one stream with one end)
+        for (int64_t &w : s->deflate_words) w = 0;
+        s->emit_eof_done = false; s->deflate_ev_n = 0;
         // (a regular file is truncated and sought to its start; what is no such file -- a pipe, a terminal -- cannot take anything back)
         struct stat st;
         if (s->emit_fd >= 0 && fstat(s->emit_fd, &st) == 0 && S_ISREG(st.st_mode) && (ftruncate(s->emit_fd, 0) != 0 || lseek(s->emit_fd, 0, SEEK_SET) != 0)) {
@@ -132,7 +136,8 @@ static int passes_tail(kvq_scan *s)
     }
     return KVQ_OK;
 }
-static void passes_landed(kvq_scan *s)
+static int emit_append(kvq_scan *s, const uint8_t *p, size_t n);
+static int passes_landed(kvq_scan *s)
 {
     for (KvqPass &p : s->passes) if (p.on) p.h.assign(p.pin, p.pin + p.words);
     if (s->reads_mode & KVQ_READ_DUPLICATION) {
@@ -165,6 +170,12 @@ static void passes_landed(kvq_scan *s)
         if (s->adapt_per) s->passes[KVQ_PASS_CLIP].h[KVQ_CLIP_PER] = s->adapt_per;
     }
     if (s->passes[KVQ_PASS_EMIT].on) s->passes[KVQ_PASS_EMIT].h[KVQ_EMIT_N] = s->emit_min;      // (the word that is no sum)
+    // the scan is over: the compressed sink gets its EOF member, once
+    if (s->passes[KVQ_PASS_EMIT].on && s->emit_compress && !s->emit_eof_done) {
+        s->emit_eof_done = true;
+        return emit_append(s, kvq_bgzf_eof(), KVQ_BGZF_EOF_BYTES);
+    }
+    return KVQ_OK;
 }
 // what an accessor hands out: the copy of a pass that is on, of a finished scan
 static const int64_t *pass_result(const kvq_scan *s, int which)
@@ -515,6 +526,18 @@ struct KvqEmitLayout {
 };
 static_assert(KvqEmitLayout::PIN_GUARDS * 8 + 2 * KvqEmitLayout::GUARD <= KvqEmitLayout::PIN_WORDS * 8, "the pieces of the emit's pinned buffer overlap");
 
+// the deflate off: its buffers given back (the stream has been waited for)
+static void deflate_off(kvq_scan *s)
+{
+    kvq_deflate_release(s->deflate); s->d_deflate_out.release();
+    if (s->deflate_pin) pinned_give(s->deflate_pin, s->deflate_pin_cap);
+    s->deflate_pin = nullptr; s->deflate_pin_cap = 0;
+    for (auto &e : s->deflate_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    s->deflate_ev.clear(); s->deflate_ev_n = 0;
+    for (int64_t &w : s->deflate_words) w = 0;
+    s->emit_compress = false; s->emit_eof_done = false;
+}
+
 static void emit_off(kvq_scan *s)
 {
     pass_off(s, s->passes[KVQ_PASS_EMIT]);               // (waits for the stream where there is anything to wait for)
@@ -524,6 +547,7 @@ static void emit_off(kvq_scan *s)
     for (hipEvent_t &e : s->emit_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     s->emit_sink.clear(); s->emit_sink.shrink_to_fit();
     s->emit_fd = -1; s->emit_min = 0; s->emit_guard_bad = 0;
+    deflate_off(s);
 }
 
 extern "C" int32_t kvq_scan_set_emit(kvq_scan *s, int32_t on, int32_t min_length)
@@ -555,6 +579,20 @@ extern "C" int32_t kvq_scan_set_emit_fd(kvq_scan *s, int32_t fd)
     s->emit_fd = fd < 0 ? -1 : fd;
     return KVQ_OK;
 }
+extern "C" int32_t kvq_scan_set_emit_compress(kvq_scan *s, int32_t on)
+{
+    kvq_clear_error();
+    if (const int rc = scan_idle(s, "kvq_scan_set_emit_compress")) return rc;
+    if (!s->passes[KVQ_PASS_EMIT].on) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_scan_set_emit_compress: the scan emits nothing (kvq_scan_set_emit first)"); return KVQ_ERR_RUNTIME; }
+    if (!on) { (void)hipStreamSynchronize(s->stream); deflate_off(s); return KVQ_OK; }
+    if (!s->deflate_pin) {
+        s->deflate_pin = (int64_t *)pinned_take(16 * 8, &s->deflate_pin_cap);
+        if (!s->deflate_pin) { kvq_set_error(KVQ_ERR_MEMORY, "cannot allocate memory for results"); return KVQ_ERR_MEMORY; }
+    }
+    s->emit_compress = true; s->emit_eof_done = false;
+    for (int64_t &w : s->deflate_words) w = 0;
+    return KVQ_OK;
+}
 // the file descriptor is about to be closed by its owner (kvq_findseqs): the sink is the host buffer again, whatever the scan holds
 static void emit_detach_fd(kvq_scan *s) { s->emit_fd = -1; }
 
@@ -571,6 +609,40 @@ static int emit_append(kvq_scan *s, const uint8_t *p, size_t n)
 }
 
 static int new_event_pair(kvq_scan *s, std::vector<KvqEventPair> &v);     // (kvq_scan.hip)
+
+// BGZF(store[0, total)) of a batch into d_deflate_out, behind the emit's kernels on the scan's stream: ONE HOST
+// WAIT for the compressed byte count and the batch's words, which join the scan's.  *src, *n: the stream that takes the text's
+// place on the way to the sink.
+static int emit_deflate(kvq_scan *s, const uint8_t *store, uint64_t total, const uint8_t **src, uint64_t *n)
+{
+    int rc;
+    const uint64_t cap = kvq_deflate_bound_bytes(total);
+    if ((rc = s->d_deflate_out.ensure((size_t)cap + 16))) return rc;
+    if (s->deflate_ev_n == s->deflate_ev.size()) {
+        KvqEventPair e(nullptr, nullptr);
+        if (hipEventCreate(&e.first) != hipSuccess || hipEventCreate(&e.second) != hipSuccess) {
+            if (e.first) (void)hipEventDestroy(e.first);
+            kvq_set_error(KVQ_ERR_DEVICE, "hipEventCreate failed"); return KVQ_ERR_DEVICE;
+        }
+        s->deflate_ev.push_back(e);
+    }
+    const KvqEventPair &ev = s->deflate_ev[s->deflate_ev_n++];
+    KVQ_HIP(hipEventRecord(ev.first, s->stream));
+    if ((rc = kvq_deflate_enqueue(store, total, s->d_deflate_out.as<uint8_t>(), cap, s->deflate, s->stream))) return rc;
+    KVQ_HIP(hipEventRecord(ev.second, s->stream));
+    KVQ_HIP(hipMemcpyAsync(s->deflate_pin, s->deflate.words.p, 16 * 8, hipMemcpyDeviceToHost, s->stream));
+    KVQ_HIP(hipStreamSynchronize(s->stream));
+    const int64_t *w = s->deflate_pin;
+    const uint64_t out = (uint64_t)w[8];
+    if (out > cap || out != (uint64_t)w[KVQ_DEFLATE_BYTES_OUT] || (uint64_t)w[KVQ_DEFLATE_BYTES_IN] != total) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "the deflate of %llu emitted bytes took %lld of them and made %llu bytes", (unsigned long long)total, (long long)w[KVQ_DEFLATE_BYTES_IN], (unsigned long long)out);
+        return KVQ_ERR_RUNTIME;
+    }
+    for (int i = 0; i < KVQ_DEFLATE_WORDS; i++)
+        s->deflate_words[i] = i == KVQ_DEFLATE_MAX_DISTANCE || i == KVQ_DEFLATE_MAX_LENGTH ? std::max(s->deflate_words[i], w[i]) : s->deflate_words[i] + w[i];
+    *src = s->d_deflate_out.as<uint8_t>(); *n = out;
+    return KVQ_OK;
+}
 
 // The emit of the R records of a batch of nbytes bytes whose index (nl4, rec_start) is on the scan's stream, behind its scan: the
 // sizes, their prefix sum, ONE HOST WAIT for the batch's byte count, the copy into the store, and the store's bytes through the two
@@ -618,9 +690,12 @@ static int emit_enqueue(kvq_scan *s, const uint8_t *d_data, int64_t nbytes, uint
     KVQ_HIP(hipMemcpyAsync(guards + KvqEmitLayout::GUARD, store + total, KvqEmitLayout::GUARD, hipMemcpyDeviceToHost, s->stream));
     const size_t H = KvqEmitLayout::HALF;
     size_t prev_n = 0;
-    for (uint64_t at = 0, i = 0; at < total; at += H, i++) {
-        const size_t n = (size_t)std::min<uint64_t>(H, total - at);
-        KVQ_HIP(hipMemcpyAsync(s->emit_pin + (i & 1) * H, store + at, n, hipMemcpyDeviceToHost, s->stream));
+    // (with kvq_scan_set_emit_compress the batch's BGZF stream takes the text's place from here on: the text stays on the device)
+    const uint8_t *store_out = store; uint64_t total_out = total;
+    if (s->emit_compress && total && (rc = emit_deflate(s, store, total, &store_out, &total_out))) return rc;
+    for (uint64_t at = 0, i = 0; at < total_out; at += H, i++) {
+        const size_t n = (size_t)std::min<uint64_t>(H, total_out - at);
+        KVQ_HIP(hipMemcpyAsync(s->emit_pin + (i & 1) * H, store_out + at, n, hipMemcpyDeviceToHost, s->stream));
         KVQ_HIP(hipEventRecord(s->emit_ev[i & 1], s->stream));
         if (i) {
             KVQ_HIP(hipEventSynchronize(s->emit_ev[(i - 1) & 1]));
@@ -629,7 +704,7 @@ static int emit_enqueue(kvq_scan *s, const uint8_t *d_data, int64_t nbytes, uint
         prev_n = n;
     }
     KVQ_HIP(hipStreamSynchronize(s->stream));
-    if (total && (rc = emit_append(s, s->emit_pin + (((total - 1) / H) & 1) * H, prev_n))) return rc;
+    if (total_out && (rc = emit_append(s, s->emit_pin + (((total_out - 1) / H) & 1) * H, prev_n))) return rc;
     for (size_t i = 0; i < 2 * KvqEmitLayout::GUARD; i++) s->emit_guard_bad += guards[i] != (uint8_t)KvqEmitLayout::GUARD_BYTE;
     return KVQ_OK;
 }
@@ -648,4 +723,18 @@ extern "C" int32_t kvq_scan_emitted(const kvq_scan *s, const uint8_t **text, int
     if (text && !s->emit_sink.empty()) *text = s->emit_sink.data();
     if (nbytes) *nbytes = (int64_t)s->emit_sink.size();
     return KVQ_OK;
+}
+
+// ---- the emit's deflate ----
+extern "C" const int64_t *kvq_scan_emit_compress(const kvq_scan *s)
+{
+    return s->passes[KVQ_PASS_EMIT].on && s->emit_compress && s->finished ? s->deflate_words : nullptr;
+}
+extern "C" double kvq_scan_emit_deflate_kernel_ms(const kvq_scan *s)
+{
+    double total = 0;
+    if (!s->emit_compress || !s->finished) return 0;
+    for (size_t i = 0; i < s->deflate_ev_n; i++) { float ms = 0; if (hipEventElapsedTime(&ms, s->deflate_ev[i].first, s->deflate_ev[i].second) == hipSuccess) total += ms; }
+    (void)hipGetLastError();
+    return total;
 }

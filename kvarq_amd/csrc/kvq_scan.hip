@@ -249,6 +249,7 @@ extern "C" void kvq_scan_destroy(kvq_scan *s)
     for (KvqPass &p : s->passes) { if (p.pin) pinned_give(p.pin, p.pin_cap); p.d.release(); }
     if (s->emit_pin) pinned_give(s->emit_pin, s->emit_pin_cap);
     for (hipEvent_t e : s->emit_ev) if (e) (void)hipEventDestroy(e);
+    deflate_off(s);
     DevBuf *bufs[] = { &s->d_emit_rec, &s->d_emit_off, &s->d_emit_bsum, &s->d_emit_store, &s->d_dup, &s->d_rkey, &s->d_roff, &s->d_rlen, &s->d_rdir, &s->d_rstore, &s->d_rsmall, &s->d_rres, &s->d_surv, &s->d_redo, &s->d_ctr_all, &s->d_gather_cnt, &s->d_gather_res, &s->d_sort_tmp, &s->d_sorted, &s->d_result, &s->d_order, &s->d_finish, &s->d_covdiff, &s->d_seg_base, &s->d_seg_cnt, &s->d_chunk_nrec, &s->d_rec_base, &s->d_nl4,
                        &s->d_rec_start, &s->d_read_off, &s->d_read_len, &s->d_arena, &s->d_blob, &s->d_small, &s->d_stage, &s->d_stage_b };
     for (DevBuf *b : bufs) b->release();

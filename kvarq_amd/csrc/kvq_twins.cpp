@@ -5,6 +5,7 @@
 // argument check serves all nine and one record walk the first eight (the emit walks with the record's first byte beside its newlines).
 #include "../../include/kvarq_hip.h"
 #include "kvq_dup_hash.h"
+#include "kvq_deflate.h"
 #include <algorithm>
 #include <string.h>
 #include <unordered_map>
@@ -409,5 +410,109 @@ extern "C" int64_t kvq_emit_host(const uint8_t *text, int64_t nbytes, const int6
         }
     }
     if (full) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_emit_host: the text emits %lld bytes, out_cap is %lld", (long long)at, (long long)out_cap); return -1; }
+    return at;
+}
+
+// ---- the emitted reads, deflated to BGZF ----
+// The definition of kvq_deflate_blocks (kernels_deflate.hip) in plain C++, over the same kvq_deflate.h: block after block, segment
+// after segment, where the kernel has a workgroup a block and a lane a segment.  (A little-endian host: the words of the bit
+// buffer are the stream's bytes.)
+struct DeflateTwinSink {
+    KvqDeflatePlan *P; uint32_t *tok; uint32_t ntok; int64_t *words;
+    void literal(uint8_t b) { tok[ntok++] = b; P->ll_freq[b]++; words[KVQ_DEFLATE_LITERALS]++; }
+    void match(uint32_t len, uint32_t dist)
+    {
+        uint32_t s, n, e;
+        tok[ntok++] = KVQ_DEFLATE_TOKEN_MATCH | (len << 16) | dist;
+        kvq_deflate_len_sym(len, s, n, e); P->ll_freq[s]++;
+        kvq_deflate_dist_sym(dist, s, n, e); P->d_freq[s]++;
+        words[KVQ_DEFLATE_MATCHES]++;
+        words[KVQ_DEFLATE_MAX_DISTANCE] = std::max<int64_t>(words[KVQ_DEFLATE_MAX_DISTANCE], dist);
+        words[KVQ_DEFLATE_MAX_LENGTH] = std::max<int64_t>(words[KVQ_DEFLATE_MAX_LENGTH], len);
+    }
+};
+
+extern "C" int64_t kvq_deflate_len(void) { return KVQ_DEFLATE_WORDS; }
+extern "C" int64_t kvq_deflate_bound(int64_t nbytes) { return nbytes < 0 ? -1 : (int64_t)kvq_deflate_bound_bytes((uint64_t)nbytes); }
+extern "C" const uint8_t *kvq_bgzf_eof(void)
+{
+    static const uint8_t eof[KVQ_BGZF_EOF_BYTES] = { 0x1F, 0x8B, 8, 4, 0, 0, 0, 0, 0, 0xFF, 6, 0, 'B', 'C', 2, 0, 0x1B, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    return eof;
+}
+
+extern "C" int32_t kvq_deflate_lengths_host(const uint32_t *freq, int32_t nsym, int32_t limit, uint8_t *lens)
+{
+    kvq_clear_error();
+    int64_t used = 0; uint64_t sum = 0;
+    for (int32_t s = 0; freq && s < nsym && s < 288; s++) { used += freq[s] != 0; sum += freq[s]; }
+    if (!freq || !lens || nsym < 0 || nsym > 288 || limit < 1 || limit > 15 || used > (1ll << limit) || sum > 0xFFFFFFFFull) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_deflate_lengths_host: bad arguments");
+        return KVQ_ERR_RUNTIME;
+    }
+    KvqDeflateWork w;
+    kvq_deflate_lengths(freq, nsym, limit, lens, &w);
+    return KVQ_OK;
+}
+
+extern "C" int64_t kvq_deflate_bgzf_host(const uint8_t *text, int64_t nbytes, uint8_t *out, int64_t out_cap, int64_t *out_words)
+{
+    kvq_clear_error();
+    if (nbytes < 0 || out_cap < 0 || !out_words || (nbytes > 0 && !text) || (out_cap > 0 && !out)) {
+        kvq_set_error(KVQ_ERR_RUNTIME, "kvq_deflate_bgzf_host: bad arguments");
+        return -1;
+    }
+    for (int i = 0; i < KVQ_DEFLATE_WORDS; i++) out_words[i] = 0;
+    uint32_t table[256];
+    for (uint32_t i = 0; i < 256u; i++) table[i] = kvq_crc_entry(i);
+    std::vector<uint8_t> own(KVQ_DEFLATE_SLOTS * KVQ_DEFLATE_SEGS), fin(KVQ_DEFLATE_SLOTS * KVQ_DEFLATE_SEGS);
+    std::vector<uint32_t> tok(KVQ_DEFLATE_BLOCK), bits(KVQ_DEFLATE_MEMBER_MAX / 4);
+    std::vector<KvqDeflatePlan> plan(1);
+    KvqDeflatePlan *const P = plan.data();
+    int64_t at = 0; bool full = false;
+    for (int64_t b0 = 0; b0 < nbytes; b0 += KVQ_DEFLATE_BLOCK) {
+        const uint8_t *blk = text + b0;
+        const uint32_t n = (uint32_t)std::min<int64_t>(KVQ_DEFLATE_BLOCK, nbytes - b0);
+        memset(P->ll_freq, 0, sizeof P->ll_freq); memset(P->d_freq, 0, sizeof P->d_freq);
+        int64_t parse[KVQ_DEFLATE_WORDS] = { 0 };               // (the parse's words count where its tokens are the stream)
+        DeflateTwinSink sink = { P, tok.data(), 0, parse };
+        uint32_t crc = 0;
+        for (uint32_t seg = 0; seg < KVQ_DEFLATE_SEGS; seg++) kvq_deflate_final_table(blk, n, seg, fin.data());
+        for (uint32_t seg = 0; seg < KVQ_DEFLATE_SEGS; seg++) {
+            kvq_deflate_parse(blk, n, seg, own.data(), fin.data(), sink);
+            // the segment's own CRC, moved to the front by the bytes behind the segment
+            const uint32_t sb = kvq_deflate_seg_begin(seg, n), se = kvq_deflate_seg_begin(seg + 1u, n);
+            crc ^= kvq_crc_mul(kvq_crc_shift(n - se), kvq_crc_bytes(table, 0u, blk + sb, se - sb));
+        }
+        P->ll_freq[256] = 1;
+        kvq_deflate_plan(P, n);
+        const uint32_t stream = kvq_deflate_stream_bytes(P, n), member = KVQ_BGZF_HEADER + stream + KVQ_BGZF_TRAILER;
+        out_words[KVQ_DEFLATE_MEMBERS]++; out_words[KVQ_DEFLATE_BYTES_IN] += n; out_words[KVQ_DEFLATE_BYTES_OUT] += member; out_words[KVQ_DEFLATE_STORED] += P->stored;
+        if (!P->stored) {
+            out_words[KVQ_DEFLATE_MATCHES] += parse[KVQ_DEFLATE_MATCHES]; out_words[KVQ_DEFLATE_LITERALS] += parse[KVQ_DEFLATE_LITERALS];
+            out_words[KVQ_DEFLATE_MAX_DISTANCE] = std::max(out_words[KVQ_DEFLATE_MAX_DISTANCE], parse[KVQ_DEFLATE_MAX_DISTANCE]);
+            out_words[KVQ_DEFLATE_MAX_LENGTH] = std::max(out_words[KVQ_DEFLATE_MAX_LENGTH], parse[KVQ_DEFLATE_MAX_LENGTH]);
+        }
+        if (at + (int64_t)member > out_cap) { full = true; at += member; continue; }
+        uint8_t *o = out + at;
+        for (uint32_t i = 0; i < KVQ_BGZF_HEADER; i++) *o++ = kvq_bgzf_header_byte(i, member);
+        if (P->stored) {
+            for (uint32_t i = 0; i < 5u; i++) *o++ = kvq_deflate_stored_byte(i, n);
+            memcpy(o, blk, n);
+        } else {
+            std::fill(bits.begin(), bits.end(), 0u);
+            KvqBitsOut<KvqPlainOr> w;
+            w.open(bits.data(), 0u);
+            kvq_deflate_put_header(P, w);
+            for (uint32_t i = 0; i < sink.ntok; i++) kvq_deflate_put_token(P, tok[i], w);
+            w.put(P->ll_code[256], P->ll_len[256]);
+            w.close();
+            memcpy(o, bits.data(), stream);
+        }
+        o += stream - (P->stored ? 5u : 0u);
+        for (uint32_t i = 0; i < 4u; i++) *o++ = (uint8_t)(crc >> (8u * i));
+        for (uint32_t i = 0; i < 4u; i++) *o++ = (uint8_t)(n >> (8u * i));
+        at += member;
+    }
+    if (full) { kvq_set_error(KVQ_ERR_RUNTIME, "kvq_deflate_bgzf_host: the text takes %lld bytes, out_cap is %lld", (long long)at, (long long)out_cap); return -1; }
     return at;
 }

@@ -239,6 +239,11 @@ def findseqs(fname, sequences, *, inflate='host', **options):
     ``words``) and 'emit_kernel_ms'.  It needs no profile.  A call that raises FastqFileFormatException
     raises it as before; what the file holds then is unspecified.
 
+    emit_compress=True beside emit=: the emitted text is deflated on the GPU and the file is BGZF -- what
+    ``samtools``, ``bwa`` and ``minimap2`` read as ``.fastq.gz``, and ``findseqs(..., inflate='device')`` too.  The path's suffix
+    decides nothing.  The dict gains 'emit_compress' (``members``, ``bytes_in``, ``bytes_out`` without the 28-byte EOF member,
+    ``stored``, ``ratio``) and 'emit_deflate_kernel_ms'.  Without emit=: ValueError.
+
     long_reads=True (not in the reference): the text is scanned on the read-list route (DESIGN section
     15) -- for reads of thousands of bases (PacBio HiFi, nanopore; FastQ or unaligned BAM), which fit
     no tile of the scan kernel and otherwise end in the exhaustive kernels: the seeded sequences are
@@ -322,6 +327,9 @@ def findseqs(fname, sequences, *, inflate='host', **options):
             from . import profile as profile_
             out['emit'] = profile_.emit_from_scan(L, h)
             out['emit_kernel_ms'] = L.kvq_scan_emit_kernel_ms(h)
+            if opt.emit_compress:
+                out['emit_compress'] = profile_.emit_compress_from_scan(L, h)
+                out['emit_deflate_kernel_ms'] = L.kvq_scan_emit_deflate_kernel_ms(h)
         return out
     finally:
         if h:

@@ -1,6 +1,6 @@
 """
 The options of a scan that are not in the reference -- ``records``, ``profile``, ``cycles``, ``long_reads``, ``per_read``,
-``duplication``, ``overrepresented``, ``adapters``, ``clip``, ``adapter_mismatches``, ``emit``, ``emit_min`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
+``duplication``, ``overrepresented``, ``adapters``, ``clip``, ``adapter_mismatches``, ``emit``, ``emit_min``, ``emit_compress`` -- said once: ``engine.findseqs`` and ``scan.Scanner`` take them as ``**options`` and normalise them here, and
 everything that passes a scan on (``Analyser.scan``, ``Fastq.profile``, ``Bam.profile``, ``profile.profile``) forwards them.
 """
 import ctypes as C
@@ -52,6 +52,18 @@ def as_emit(emit, emit_min=None):
     return emit, m
 
 
+def as_emit_compress(emit_compress, emit):
+    """the ``emit_compress`` option beside a normalised ``emit``: None or False -> False; True -> True; anything else, and True
+    without ``emit``: ValueError"""
+    if emit_compress is None:
+        return False
+    if not isinstance(emit_compress, bool):
+        raise ValueError('emit_compress is a bool')
+    if emit_compress and emit is None:
+        raise ValueError('emit_compress= is the form of what emit= writes: give emit= too')
+    return emit_compress
+
+
 class ScanOptions(object):
     """``records``: keep the FastQ record of every hit; ``profile``: the cutoffs of the input's profile
     (``profile.as_cutoffs``; True: ``amin``, or the configured Amin; None: no profile) -- a list of byte values here;
@@ -68,11 +80,13 @@ class ScanOptions(object):
     ``emit``: the reads the scan saw, as FastQ text -- None or False: off; True: handed back (``Scanner``); a path:
     streamed there (``findseqs`` takes nothing else) -- True or the path's bytes here; ``emit_min``: the shortest read it keeps -- None:
     the configured minreadlength, -1 here; an int >= 0 as given; anything else, and without ``emit``: ValueError (``as_emit``).  It
-    needs no profile."""
+    needs no profile.  ``emit_compress``: the emitted text leaves the GPU as BGZF, deflated there (DESIGN section 23) -- a bool;
+    anything else, and True without ``emit``: ValueError.  The path's suffix decides nothing."""
 
     def __init__(self, records=False, profile=None, cycles=False, long_reads=False, per_read=False, duplication=False, overrepresented=False,
-                 adapters=None, clip=None, amin=None, adapter_mismatches=None, emit=None, emit_min=None):
+                 adapters=None, clip=None, amin=None, adapter_mismatches=None, emit=None, emit_min=None, emit_compress=None):
         self.emit, self.emit_min = as_emit(emit, emit_min)
+        self.emit_compress = as_emit_compress(emit_compress, self.emit)
         self.long_reads, self.long_mode = long_reads, _lib.long_reads_mode(long_reads)
         self.records, self.cycles, self.overrepresented = bool(records), bool(cycles), bool(overrepresented)
         self.read_stats = (_lib.READ_STATS if per_read else 0) | (_lib.READ_DUPLICATION if duplication else 0)
@@ -134,7 +148,7 @@ class ScanOptions(object):
         if isinstance(o, _lib.FindOptsAdapters):
             o = _lib.FindOptsAdaptersMm(o, 0)
         e = _lib.FindOptsEmit(o, self.emit_min, self.emit)
-        e.m.a.base.size, e.m.a.base.flags = C.sizeof(_lib.FindOptsEmit), e.m.a.base.flags | _lib.FIND_EMIT
+        e.m.a.base.size, e.m.a.base.flags = C.sizeof(_lib.FindOptsEmit), e.m.a.base.flags | _lib.FIND_EMIT | (_lib.FIND_EMIT_BGZF if self.emit_compress else 0)
         return e
 
     def setters(self):
@@ -160,4 +174,6 @@ class ScanOptions(object):
             calls.append(('kvq_scan_set_long_reads', (self.long_mode,)))
         if self.emit is not None:
             calls.append(('kvq_scan_set_emit', (1, self.emit_min)))      # (a path: the caller opens it and hands it over, kvq_scan_set_emit_fd)
+            if self.emit_compress:
+                calls.append(('kvq_scan_set_emit_compress', (1,)))
         return calls

@@ -277,6 +277,7 @@ class Profile(object):
         self.adapters = adapters
         self.clipped = None                     # the ``Clip`` of a scan with ``clip=`` (set by ``profile`` and ``profile_host``)
         self.emitted = None                     # the ``Emit`` of a scan with ``emit=`` (set by ``profile``)
+        self.emit_compressed = None             # what the emit's deflate did, with ``emit_compress=True`` (set by ``profile``)
         self.over = self.over_info = self.overrepresented = None
         if over is not None:
             self.over = np.array(over, dtype=np.int64)
@@ -754,6 +755,54 @@ def emitted_from_scan(L, h):
     return np.frombuffer(C.string_at(ptr.value, n.value) if n.value else b'', dtype=np.uint8)
 
 
+DEFLATE_LEN = 8                                              # (include/kvarq_hip.h: kvq_deflate_len())
+DEFLATE_FIELDS = ('members', 'bytes_in', 'bytes_out', 'stored', 'matches', 'literals', 'max_distance', 'max_length')
+
+
+def deflate_words(w):
+    """the words of a deflate as a dict: ``DEFLATE_FIELDS``, ``ratio`` (bytes in per byte out; nan for an empty text), ``words``"""
+    w = np.asarray(w, dtype=np.int64)
+    assert w.shape == (DEFLATE_LEN,)
+    d = dict((name, int(w[k])) for k, name in enumerate(DEFLATE_FIELDS))
+    d['ratio'] = d['bytes_in'] / float(d['bytes_out']) if d['bytes_out'] else float('nan')
+    d['words'] = w
+    return d
+
+
+def emit_compress_from_scan(L, h):
+    """what the emit's deflate of a finished scan object did (kvq_scan_emit_compress), None when it is off"""
+    ptr = L.kvq_scan_emit_compress(h)
+    return deflate_words(np.ctypeslib.as_array(ptr, shape=(DEFLATE_LEN,)).copy()) if ptr else None
+
+
+def bgzf_eof():
+    """the 28 bytes of the BGZF EOF member (kvq_bgzf_eof)"""
+    return C.string_at(_lib.lib().kvq_bgzf_eof(), 28)
+
+
+def deflate_bgzf_host(text, cap=None):
+    """the CPU twin of the emit's deflate (kvq_deflate_bgzf_host) over a text in host memory: (BGZF(text) as bytes -- the members,
+    without the EOF member --, the eight words).  The output buffer is exactly kvq_deflate_bound(len(text)) long, or ``cap``"""
+    L = _lib.lib()
+    arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, dtype=np.uint8)
+    out = np.empty(L.kvq_deflate_bound(arr.nbytes) if cap is None else cap, dtype=np.uint8)
+    words = np.zeros(DEFLATE_LEN, dtype=np.int64)
+    n = L.kvq_deflate_bgzf_host(arr.ctypes.data if arr.nbytes else None, arr.nbytes, out.ctypes.data if out.nbytes else None, out.nbytes,
+                                words.ctypes.data_as(C.POINTER(C.c_int64)))
+    if n < 0:
+        raise RuntimeError(_lib.last_error()[1])
+    return out[:n].tobytes(), words
+
+
+def deflate_lengths_host(freq, limit):
+    """the length-limited code builder on its own (kvq_deflate_lengths_host): the code lengths of a histogram, a uint8 array"""
+    f = np.ascontiguousarray(freq, dtype=np.uint32)
+    lens = np.zeros(len(f), dtype=np.uint8)
+    if _lib.lib().kvq_deflate_lengths_host(f.ctypes.data, len(f), limit, lens.ctypes.data):
+        raise RuntimeError(_lib.last_error()[1])
+    return lens
+
+
 def emit_host(text, amin, min_length, chunk_off=None, into=None):
     """the CPU twin of the emit (kvq_emit_host) over a text in host memory: (EMIT(text) as a new uint8 array, the eight words).
     ``amin``: a byte value, a character or a byte; ``into``: words to add to, as the twin does.  The output buffer is exactly the
@@ -869,7 +918,8 @@ def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     content of these probes (``as_adapters``); ``clip``: of the input with the scores of its adapters masked (DESIGN section 19;
     ``Profile.clipped``: the ``Clip``); ``adapter_mismatches``: the probes of both tolerate mismatches (DESIGN section 20);
     ``emit`` (a path) / ``emit_min``: the input's reads, trimmed (and clipped, with ``clip``), are written there as FastQ (DESIGN
-    section 21; ``Profile.emitted``: the ``Emit``) -- a BAM thereby becomes trimmed FastQ;
+    section 21; ``Profile.emitted``: the ``Emit``) -- a BAM thereby becomes trimmed FastQ; ``emit_compress``: that file is BGZF,
+    deflated on the GPU (DESIGN section 23; ``Profile.emit_compressed``: the dict of ``deflate_words``);
     ``long_reads``: as for
     ``engine.findseqs``, which takes the ``options``"""
     from . import engine
@@ -877,6 +927,7 @@ def profile(fnames, cutoffs=True, inflate='host', sources=None, **options):
     p = r['profile']
     p.clipped = r.get('clip')
     p.emitted = r.get('emit')                   # the ``Emit`` of a call with ``emit=`` (the text is in the file)
+    p.emit_compressed = r.get('emit_compress')  # what its deflate did, with ``emit_compress=True``
     if sources is not None and p.over is not None:
         p.relabel(sources)
     return p
@@ -900,9 +951,12 @@ def main(argv=None):
                     help='with --adapters or --clip: the probes tolerate one mismatch per PER bases (10 .. 32; without a value: 10); the adapter lines gain the counts of first occurrences with 0/1/2/3 mismatches')
     ap.add_argument('--emit', metavar='OUT', help='write the reads as the scan saw them -- cut to the quality trim at the configured Amin, behind --clip to the adapter too -- to OUT as FastQ, all files to the one output')
     ap.add_argument('--emit-min', type=int, default=None, metavar='N', help='with --emit: keep reads of N bases and more (default: the configured minreadlength; 0 keeps every record, so that the files of two mates stay in step)')
+    ap.add_argument('--emit-bgzf', action='store_true', help='with --emit: OUT is BGZF (.fastq.gz as samtools, bwa and minimap2 read it), deflated on the GPU; the name of OUT decides nothing')
     a = ap.parse_args(argv)
     if a.emit_min is not None and (a.emit is None or a.emit_min < 0):
         ap.error('--emit-min takes N >= 0 and needs --emit')
+    if a.emit_bgzf and a.emit is None:
+        ap.error('--emit-bgzf needs --emit')
     if a.adapter_mismatches is not None and a.adapters is None and a.clip is None:
         ap.error('--adapter-mismatches needs --adapters or --clip')
     if a.adapter_mismatches is not None and not 10 <= a.adapter_mismatches <= 32:
@@ -924,6 +978,8 @@ def main(argv=None):
         more['emit'] = a.emit
         if a.emit_min is not None:
             more['emit_min'] = a.emit_min
+        if a.emit_bgzf:
+            more['emit_compress'] = True
     p = profile(a.files, cutoffs=True, inflate=a.inflate, **({} if a.quality else more))
     if a.quality:
         dQ = p.dQ()
@@ -943,6 +999,9 @@ def main(argv=None):
         print(p.clipped.line())
     if a.emit is not None:
         print(p.emitted.line())
+        if a.emit_bgzf:
+            z = p.emit_compressed
+            print('emit bgzf: members=%d stored=%d bytes %d -> %d (%.3f)' % (z['members'], z['stored'], z['bytes_in'], z['bytes_out'] + 28, z['ratio']))
 
 
 if __name__ == '__main__':

@@ -92,7 +92,7 @@ class Scanner(object):
 
     def __init__(self, table, counters_ptr=None, retain_limit=1 << 30, replay=None, **options):
         self.table = table
-        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters, clip, emit, emit_min (``options.ScanOptions``), set on the
+        # records, profile (True: the table's Amin), cycles, long_reads, per_read, duplication, overrepresented, adapters, clip, emit, emit_min, emit_compress (``options.ScanOptions``), set on the
         # scan handle once and kept across reset
         opt = ScanOptions(amin=bytes([table.config.Amin & 0xFF]), **options)
         self.records, self.profile, self.cycles, self.read_stats, self.long_reads = opt.records, opt.profile, opt.cycles, opt.read_stats, opt.long_reads
@@ -102,6 +102,7 @@ class Scanner(object):
         # ``emit=True``: ``finish`` hands the emitted text back ('emitted'); ``emit=<path>``: it is streamed to that file, which is
         # created here and stays open until ``close``; ``emit_min``: the shortest read kept
         self.emit, self.emit_min, self._emit_file = opt.emit, opt.emit_min, None
+        self.emit_compress = opt.emit_compress      # the emitted text leaves the GPU as BGZF: 'emitted' and the file hold that
         self.h = _lib.lib().kvq_scan_create(table.h, counters_ptr)
         if not self.h:
             _raise_last()
@@ -216,6 +217,9 @@ class Scanner(object):
             from . import profile as profile_
             out['emit'] = profile_.emit_from_scan(L, self.h)
             out['emit_kernel_ms'] = L.kvq_scan_emit_kernel_ms(self.h)
+            if self.emit_compress:
+                out['emit_compress'] = profile_.emit_compress_from_scan(L, self.h)
+                out['emit_deflate_kernel_ms'] = L.kvq_scan_emit_deflate_kernel_ms(self.h)
             if self.emit is True:
                 out['emitted'] = profile_.emitted_from_scan(L, self.h)      # the emitted FastQ text, a numpy.uint8 array
         out['kernel_ms'] = L.kvq_scan_kernel_ms(self.h)
@@ -383,6 +387,17 @@ def inflate_bgzf_device(d_in, in_bytes, d_blocks, nblocks, d_out, out_bytes, d_s
     addresses as ints (e.g. torch tensors' data_ptr()).  Blocks until done."""
     _check(_lib.lib().kvq_inflate_bgzf_device(C.c_void_p(d_in), in_bytes, C.c_void_p(d_blocks), nblocks,
                                                C.c_void_p(d_out), out_bytes, C.c_void_p(d_status)))
+
+
+def deflate_bgzf_device(d_text, nbytes, d_out, out_cap):
+    """kvq_deflate_bgzf_device: BGZF(d_text[0, nbytes)) -- the members, without the EOF member -- into
+    d_out[0, out_cap), both device addresses as ints; ``kvq_deflate_bound(nbytes)`` bytes always hold it.  Returns (its length, the
+    eight words); RuntimeError when out_cap is too small.  Blocks until done."""
+    words = np.zeros(8, dtype=np.int64)
+    n = _lib.lib().kvq_deflate_bgzf_device(C.c_void_p(d_text), nbytes, C.c_void_p(d_out), out_cap, words.ctypes.data_as(C.POINTER(C.c_int64)))
+    if n < 0:
+        _raise_last()
+    return n, words
 
 
 def inflate_gzip_device(d_file, n, chunk_bytes, d_out, out_cap):
