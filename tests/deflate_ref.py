@@ -39,6 +39,45 @@ def final_table(block, seg):
     return tab
 
 
+def parse(block):
+    """the parse of one block (at most BLOCK bytes) as kvq_deflate.h states it in words -> its tokens in the form of ``tokens``:
+    ints for literals, (length, distance) for matches.  Segment s of SEG bytes is parsed greedily from its first byte.  At a
+    position p with p + 3 <= the segment's end the candidates are, in this order, the last position in front of p in the segment
+    whose three bytes hash as p's do (its own running table), and what the FINAL tables of the segments s - 1 and s - 2 hold for
+    that hash; a candidate's match is the common prefix of the raw block at both positions, cut at the segment's end; the longest
+    wins, the first among equals; three bytes or more are a match, else block[p] is a literal.  Every position i with i + 3 <= n
+    is entered into the running table, those inside a match too."""
+    block = bytes(block)
+    n = len(block)
+    assert n <= BLOCK
+    toks = []
+    hashes = [hash3(block[i:i + 3]) for i in range(n - 2)]                        # of every position i with i + 3 <= n
+    finals =[final_table(block, s) for s in range((n + SEG - 1) // SEG)]         # (functions of the text, not of any parse)
+    for s in range(len(finals)):
+        end = min((s + 1) * SEG, n)
+        own = {}
+        tables = [own] + [finals[s - back] for back in range(1, REACH + 1) if s - back >= 0]
+        p = s * SEG
+        while p < end:
+            best = best_q = 0
+            if p + 3 <= end:
+                for table in tables:
+                    q = table.get(hashes[p])
+                    if q is None:
+                        continue
+                    k = 0
+                    while p + k < end and block[q + k] == block[p + k]:
+                        k += 1
+                    if k > best:
+                        best, best_q = k, q
+            step = best if best >= 3 else 1
+            toks.append((best, p - best_q) if best >= 3 else block[p])
+            for i in range(p, min(p + step, n - 2)):
+                own[hashes[i]] = i
+            p += step
+    return toks
+
+
 def repeats(text):
     """the trigrams of a text that occur more than once"""
     seen, twice = set(), set()
@@ -64,10 +103,11 @@ def members(out):
 
 class _Bits(object):
     def __init__(self, data):
-        self.v, self.at = int.from_bytes(data, 'little'), 0
+        self.d, self.at = bytes(data), 0
 
     def get(self, n):
-        r = (self.v >> self.at) & ((1 << n) - 1)
+        """the next n <= 16 bits, the first the lowest (bits behind the data's end read as 0)"""
+        r = (int.from_bytes(self.d[self.at >> 3:(self.at >> 3) + 4], 'little') >> (self.at & 7)) & ((1 << n) - 1)
         self.at += n
         return r
 

@@ -44,6 +44,43 @@ def test_the_twin_on_every_text(name):
     assert again == out and (words2 == words).all()
 
 
+def stream_and_parse(text):
+    """[(the tokens of a BTYPE-2 member of the twin's stream, the tokens ``deflate_ref.parse`` gives its block)]"""
+    out, _ = P.deflate_bgzf_host(text)
+    pairs, at = [], 0
+    for _, _, payload, _, isize in D.members(out):
+        if (payload[0] >> 1) & 3 == 2:
+            pairs.append((D.tokens(payload)['tokens'], D.parse(text[at:at + isize])))
+        at += isize
+    return pairs
+
+
+@pytest.mark.parametrize('name', D.NAMES)
+def test_the_parse_as_stated_in_python(name):
+    """the rule of the parse that kvq_deflate.h states in words, as ``deflate_ref.parse``: the tokens of every BTYPE-2 member are
+    the rule's, one for one -- not only within its limits (``check_tokens``)"""
+    pairs = stream_and_parse(D.text(name))
+    # fifteen members in all: a member of one byte is stored, as are those of 'random'
+    assert len(pairs) == {'empty': 0, 'one': 0, 'random': 0, 'two-blocks+1': 2, 'one-byte': 2, 'block-end': 2}.get(name, 1)
+    for got, want in pairs:
+        assert got == want
+
+
+def test_the_parse_on_the_emitted_text_of_generated_cases():
+    """the first member of the emitted text of every case of group 0 of tests/fuzz_passes.py"""
+    import fuzz_passes as Z
+    n = 0
+    for seed, seeded in Z.group(0):
+        c, r = Z.case(seed, seeded), Z.refs(seed, seeded)
+        if not r.accepted:
+            continue
+        text = r.emit_of(c.text, r.co, c.cfg['minreadlength'])[0][:D.BLOCK]
+        for got, want in stream_and_parse(text):
+            assert got == want, seed
+            n += 1
+    assert n >= 10
+
+
 def test_the_eof_member_and_the_bound():
     L = _lib.lib()
     assert P.bgzf_eof() == D.EOF and L.kvq_deflate_len() == D.LEN

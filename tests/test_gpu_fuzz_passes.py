@@ -7,7 +7,13 @@ cases; ``scan.Scanner`` under chunk cuts and batch cuts of the test's choosing, 
 quantity is an integer or a byte string: the comparisons are exact.  tests/test_fuzz_passes_host.py asserts on the CPU what the
 slice reaches and that the references agree among themselves on it.
 
-The cases come in NGROUPS groups of about 15, a leg and a group a test.  A test ends by asserting that what the leg compared --
+Four more legs take the emit, its deflate and the tolerant adapter probes through the same files: ``emit=`` on ``findseqs`` beside
+every pass, beside the tolerant clip, deflated, and on the read-list route; the emit on the BGZF, gzip and BAM routes, with the
+BGZF it wrote read back in on the device-inflate route; ``Scanner(emit=True)`` under the cuts of the scanner leg, deflated on
+every other feeding, with the arena replay, and the tokens of a deflated member against ``deflate_ref.parse``;
+``adapter_mismatches=`` against the Hamming loop of ``adapt_mm_ref``, in the content pass, the clip and a ``Scanner`` batch.
+
+The cases come in NGROUPS groups of about 15 (the four newer legs, whose references take longer: NGROUPS_NEW groups of 5), a leg and a group a test.  A test ends by asserting that what the leg compared --
 cases, hits, refusals, files of every route -- is what the references say of its group (``fuzz_passes.expected``), so a leg that
 left something out fails in the group where it did; the host test asserts that those figures, summed over the groups, reach the
 floors of ``fuzz_passes.LEG_FLOORS``.  No test depends on another having run.
@@ -30,12 +36,12 @@ def no_knobs(monkeypatch):
     monkeypatch.delenv('KVQ_ARENA_CAP', raising=False)
 
 
-@pytest.mark.parametrize('group', range(Z.NGROUPS))
-@pytest.mark.parametrize('leg', [name for name, _ in Z.LEGS])
+@pytest.mark.parametrize('leg,group', [pytest.param(name, i, id='%s-%d' % (name, i)) for name, _ in Z.LEGS for i in range(Z.ngroups(name))])
 def test_generated_cases(leg, group, tmp_path, monkeypatch):
     assert not BROKEN, 'not run: an earlier case ended in an error of the runtime, %s' % BROKEN[0]
     tally = collections.Counter()
-    for seed, seeded in Z.group(group):
+    cases = Z.group(group, Z.ngroups(leg))
+    for seed, seeded in cases:
         if leg == 'long_reads' and not seeded:
             continue
         c, r = Z.case(seed, seeded), Z.refs(seed, seeded)
@@ -48,7 +54,7 @@ def test_generated_cases(leg, group, tmp_path, monkeypatch):
         except Exception as e:
             BROKEN.append('seed %d (%s), leg %s: %r' % (seed, 'seeded' if seeded else 'general', leg, e))
             raise
-    want = Z.expected(leg, Z.group(group))
+    want = Z.expected(leg, cases)
     print(leg, group, dict(tally))
     for key in set(want) | (set(tally) - {'read list', 'hits of the BAM'}):
         assert tally[key] == want[key], (key, tally[key], want[key])
